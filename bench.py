@@ -2,6 +2,7 @@
 """bench.py -- bodies/sec of the STRAPS hot path on MI355X (driver contract in the task prompt).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|fwd|smpl | --config 1..4] [--batch B] [--layers 18|50]
+    python bench.py ... --dump-outputs DIR    (also write the last timed step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch; inputs are generated / resident in HBM:
@@ -407,6 +408,38 @@ def instrument(timer):
     return proxy
 
 
+DUMP_MAX_BODIES = 256          # --dump-outputs: per-body outputs of larger batches are written for a fixed, seeded sample of this many bodies
+DUMP_MAX_PARAMS = 1 << 20      # ... and the parameter vector for a fixed, seeded sample of this many entries
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs, B):
+    """write what the timed path computed in its last step: `outs` maps a name to a device tensor, either one row per body (leading
+    dimension B) or, for 'loss' and 'params', a whole-step record.  Copied to the host as float32 right after the timed region (later
+    passes overwrite the graph's buffers and the parameters).  The sample indices depend only on the sizes, so two runs with the same
+    arguments write the same entries."""
+    import numpy as np
+    rows = None
+    if B > DUMP_MAX_BODIES:
+        rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(B, DUMP_MAX_BODIES, replace=False)))
+    host = {}
+    for name, t in outs.items():
+        t = t.detach().float().cpu()
+        if name == 'params':
+            t = t.reshape(-1)
+            if t.numel() > DUMP_MAX_PARAMS:
+                t = t[torch.from_numpy(np.sort(np.random.default_rng(1).choice(t.numel(), DUMP_MAX_PARAMS, replace=False)))]
+        elif name != 'loss' and rows is not None:
+            t = t.index_select(0, rows)
+        host[name] = t.contiguous().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -458,6 +491,9 @@ def main():
                     help="measure roofline.traffic in this run (two short rocprofv3 counter passes after the timed region) instead of reading the "
                          "committed profiles/pmc_traffic.json; on by default for the driver-style default call")
     ap.add_argument('--no-measure-traffic', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; rank 0; "
+                         "a fixed, seeded sample of bodies / parameters where the outputs exceed 64 MB)")
     ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)      # (a pass launched by the headline run for 'other_configs')
     args = ap.parse_args()
     # the driver's one call (no --workload / --config / --layers / --batch) also times the other GPU configurations, each in a child process of
@@ -567,7 +603,8 @@ def main():
             with torch.no_grad():
                 cam, pose, shape = reg(x)
                 R = straps_amd.rot6d_to_rotmat(pose).view(-1, 24, 3, 3)
-                return smpl.forward_arrays(shape.contiguous(), R)[0]
+                verts, joints = smpl.forward_arrays(shape.contiguous(), R)
+                return {'pred_cam': cam, 'pred_rotmats': R, 'pred_shape': shape, 'pred_verts': verts, 'pred_joints': joints}
         workload = 'configs[1]: %s encoder + 3-iter IEF + rot6d + SMPL forward-only, 18x256x256 proxy' % net
         dominant = 'conv_igemm_x3_kernel' if args.conv_precision == 'bf16x3' else 'conv_igemm_kernel'
         par = 'bodies sharded over %d rank(s), no collective (forward)' % world
@@ -580,7 +617,8 @@ def main():
         smpl_precision = args.smpl_precision
 
         def step():
-            return smpl.forward_arrays(betas, R, want_joints=True, precision=smpl_precision, kernel=args.smpl_kernel)[0]
+            verts, joints = smpl.forward_arrays(betas, R, want_joints=True, precision=smpl_precision, kernel=args.smpl_kernel)
+            return {'verts': verts, 'joints': joints}
         workload = 'configs[4]: SMPL-only forward, %d random (theta,beta) per step x %d steps = %d bodies -> 6890-vertex meshes + 90 joints' % (
             B, args.steps, B * args.steps)
         dominant = 'smpl_fwd'
@@ -588,6 +626,7 @@ def main():
 
     graph_mode = not args.no_graph
     fwd_graph = None
+    graph_out = None                   # (the captured forward's output tensors: every replay rewrites them)
     for _ in range(max(args.warmup, 3 if graph_mode else 0)):
         step()
     torch.cuda.synchronize()
@@ -596,7 +635,7 @@ def main():
         try:
             fwd_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(fwd_graph, capture_error_mode='thread_local'):
-                step()
+                graph_out = step()
             run = fwd_graph.replay
         except Exception as e:                 # noqa: BLE001 -- eager launches of the same kernels
             sys.stderr.write('hipGraph capture failed (%s); timing eager launches\n' % (e,))
@@ -614,7 +653,7 @@ def main():
     probe.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last_out = run()
     torch.cuda.synchronize()
     local_elapsed = time.perf_counter() - t0
     if dist is not None:
@@ -623,6 +662,15 @@ def main():
     elapsed = time.perf_counter() - t0
     timer.on = False
     sclk_mhz = probe.mhz()
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        if args.workload == 'train':
+            last = ts.last                 # (the buffers the last timed step wrote; its loss record is the step's return value)
+            est = last['est']
+            outs = {'loss': last['loss'], 'pred_cam': est[:, :3], 'pred_rotmats': last['rot'], 'pred_shape': est[:, 147:157],
+                    'pred_verts': last['verts'], 'pred_joints': last['joints'], 'params': ts.flat_p}
+        else:
+            outs = graph_out if graph_mode else last_out
+        dump_outputs(args.dump_outputs, outs, B)
     exposed_exchange_ms = None
     if args.workload == 'train':
         ts.time_exchange = False
