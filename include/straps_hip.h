@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define STRAPS_ABI_VERSION 9
+#define STRAPS_ABI_VERSION 10
 
 #define STRAPS_OK 0
 #define STRAPS_EINVAL 1       /* bad argument (shape, alignment, null pointer) */
@@ -201,6 +201,11 @@ int straps_rot6d_fwd(const float* x6, long long ld, int per_row, float* rotmats,
                      void* stream);
 /* axis-angle [n][3] -> R [n][3][3] (angle = ||r + 1e-8||).                                      */
 int straps_rodrigues_fwd(const float* aa, float* rotmats, long long n, void* stream);
+/* gradient of straps_rodrigues_fwd: aa [n][3], drotmats = dL/dR [n][3][3] -> daa [n][3].  The exact derivative of the
+ * formula the forward evaluates (autograd of angle = ||r + 1e-8||, d = r / angle, R = I + sin K + (1 - cos) K^2,
+ * K = skew(d)), the +1e-8 included: a zero row gives the finite vee(antisymmetric part of dR) autograd gives there.
+ * One lane per rotation, fp32.                                                                  */
+int straps_rodrigues_bwd(const float* aa, const float* drotmats, float* daa, long long n, void* stream);
 /* utils/cam_utils.py:5-26 orthographic_project_torch: points [batch][n][3], cam rows [s, tx, ty] (row stride ld_cam)
  * -> out [batch][n][2] = s * (x + tx, y + ty); and its gradient (dpoints [batch][n][3] and / or dcam [batch][3]; per-body
  * sums in a fixed order).                                                                          */
@@ -326,6 +331,15 @@ size_t straps_smpl_bwd_workspace_bytes(long long batch, int chunks);
 int straps_smpl_bwd(const straps_smpl_model_t* model, const float* betas, const float* rotmats,
                     const float* dverts, const float* djoints, float* dbetas, float* drotmats,
                     void* workspace, long long batch, int chunks, void* stream);
+/* the same gradient for an axis-angle pose (smplx's pose2rot=True): rotmats [B,24,3,3] = straps_rodrigues_fwd of
+ * full_pose_aa [B,72] (global orientation first) -> dbetas [B,10] and dfull_pose_aa [B,72], the Rodrigues derivative
+ * applied in the epilogue of the pose pass (bit-identical to straps_smpl_bwd followed by straps_rodrigues_bwd).
+ * drotmats [B,24,3,3] may be NULL; when given it receives what straps_smpl_bwd writes there.  Workspace size:
+ * straps_smpl_bwd_workspace_bytes(batch, chunks).                                                 */
+int straps_smpl_bwd_aa(const straps_smpl_model_t* model, const float* betas, const float* rotmats,
+                       const float* full_pose_aa, const float* dverts, const float* djoints, float* dbetas,
+                       float* dfull_pose_aa, float* drotmats, void* workspace, long long batch, int chunks,
+                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backward of the encoder / IEF / rot6d -- the work of loss.backward() (train loop :232) that

@@ -453,6 +453,27 @@ def rot6d_autograd(x):
     return _Rot6dFn.apply(x)
 
 
+class _RodriguesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        from .rigid_transform_utils import _rodrigues_fwd
+        ctx.save_for_backward(x)
+        return _rodrigues_fwd(x.detach())
+
+    @staticmethod
+    def backward(ctx, dR):
+        (x,) = ctx.saved_tensors
+        r = x.detach().contiguous().view(-1, 3)
+        daa = torch.empty(r.shape[0], 3, device=r.device, dtype=torch.float32)
+        hipabi.check(hipabi.lib().straps_rodrigues_bwd(hipabi.ptr(r), hipabi.ptr(dR.contiguous()), hipabi.ptr(daa), r.shape[0], hipabi.stream_ptr()),
+                     'straps_rodrigues_bwd')
+        return daa.view(x.shape)
+
+
+def rodrigues_autograd(x):
+    return _RodriguesFn.apply(x)
+
+
 class _SmplFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, smpl, betas, rotmats):
@@ -478,3 +499,40 @@ class _SmplFn(torch.autograd.Function):
 
 def smpl_forward_autograd(smpl, betas, rotmats):
     return _SmplFn.apply(smpl, betas, rotmats)
+
+
+class _SmplAaFn(torch.autograd.Function):
+    """SMPL on an axis-angle pose (pose2rot=True): forward = straps_rodrigues_fwd + the forward kernels (the outputs of the no-grad path, bit for
+    bit); backward = straps_smpl_bwd_aa, the Rodrigues derivative fused into the pose pass of the SMPL gradient."""
+
+    @staticmethod
+    def forward(ctx, smpl, betas, full_pose_aa):
+        from .rigid_transform_utils import _rodrigues_fwd
+        # both inputs checked before the first launch (a CPU body_pose left in fitting code must raise, not reach a kernel as a host pointer);
+        # betas as straps_smpl_bwd's path takes them (any float dtype, converted), the pose as batch_rodrigues takes it (fp32 only)
+        hipabi.require_gpu_tensor(betas, 'betas')
+        hipabi.require_gpu_tensor(full_pose_aa, 'axis-angle pose (global_orient, body_pose)', torch.float32)
+        B = betas.shape[0]
+        b, aa = betas.detach().float().contiguous(), full_pose_aa.detach().float().contiguous()
+        r = _rodrigues_fwd(aa.view(-1, 3)).view(B, 24, 3, 3)
+        verts, joints = smpl.forward_arrays(b, r)
+        ctx.smpl, ctx.b, ctx.aa, ctx.r = smpl, b, aa, r
+        return verts, joints
+
+    @staticmethod
+    def backward(ctx, dverts, djoints):
+        smpl, b, aa, r = ctx.smpl, ctx.b, ctx.aa, ctx.r
+        L = hipabi.lib()
+        B = b.shape[0]
+        dbetas = torch.empty_like(b)
+        daa = torch.empty(B, 72, device=b.device, dtype=torch.float32)
+        ws = torch.empty(L.straps_smpl_bwd_workspace_bytes(B, 0) // 4, device=b.device, dtype=torch.float32)
+        dv = dverts.contiguous() if dverts is not None else None
+        dj = djoints.contiguous() if djoints is not None else None
+        hipabi.check(L.straps_smpl_bwd_aa(C.byref(smpl._model_struct()), hipabi.ptr(b), hipabi.ptr(r), hipabi.ptr(aa), hipabi.ptr(dv), hipabi.ptr(dj),
+                                          hipabi.ptr(dbetas), hipabi.ptr(daa), None, hipabi.ptr(ws), B, 0, hipabi.stream_ptr()), 'straps_smpl_bwd_aa')
+        return None, dbetas, daa
+
+
+def smpl_aa_forward_autograd(smpl, betas, full_pose_aa):
+    return _SmplAaFn.apply(smpl, betas, full_pose_aa)

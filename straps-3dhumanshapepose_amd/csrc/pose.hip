@@ -1,5 +1,6 @@
 // pose.hip -- rotation representations (utils/rigid_transform_utils.py:27-41; smplx batch_rodrigues)
 #include "common.h"
+#include "rodrigues.h"
 
 namespace {
 
@@ -42,6 +43,21 @@ __global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void rodrigues_kernel(co
     o[0] = 1.0f + c1 * q00;           o[1] = s * k01 + c1 * q01;        o[2] = s * k02 + c1 * q02;
     o[3] = s * k10 + c1 * q10;        o[4] = 1.0f + c1 * q11;           o[5] = s * k12 + c1 * q12;
     o[6] = s * k20 + c1 * q20;        o[7] = s * k21 + c1 * q21;        o[8] = 1.0f + c1 * q22;
+}
+
+// its gradient: one lane per rotation, the derivative of rodrigues.h (shared with the fused epilogue of smpl_pose_bwd_kernel)
+__global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void rodrigues_bwd_kernel(const float* __restrict__ aa, const float* __restrict__ dR,
+                                                                                 float* __restrict__ daa, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float g[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) g[e] = dR[i * 9 + e];
+    float ox, oy, oz;
+    straps_rodrigues_bwd_one(aa[i * 3 + 0], aa[i * 3 + 1], aa[i * 3 + 2], g, ox, oy, oz);
+    daa[i * 3 + 0] = ox;
+    daa[i * 3 + 1] = oy;
+    daa[i * 3 + 2] = oz;
 }
 
 // ---- camera projections of the module-level helpers (utils/cam_utils.py:5-26, 40-71) ----
@@ -142,5 +158,13 @@ extern "C" int straps_rodrigues_fwd(const float* aa, float* rotmats, long long n
     STRAPS_REQUIRE(aa && rotmats && n > 0, "straps_rodrigues_fwd: bad arguments");
     hipLaunchKernelGGL(rodrigues_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, aa, rotmats, n);
     STRAPS_CHECK_LAUNCH("rodrigues_kernel");
+    return STRAPS_OK;
+}
+
+extern "C" int straps_rodrigues_bwd(const float* aa, const float* drotmats, float* daa, long long n, void* stream) {
+    STRAPS_REQUIRE(aa && drotmats && daa, "straps_rodrigues_bwd: null pointer");
+    STRAPS_REQUIRE(n > 0, "straps_rodrigues_bwd: n must be positive (got %lld)", n);
+    hipLaunchKernelGGL(rodrigues_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, aa, drotmats, daa, n);
+    STRAPS_CHECK_LAUNCH("rodrigues_bwd_kernel");
     return STRAPS_OK;
 }

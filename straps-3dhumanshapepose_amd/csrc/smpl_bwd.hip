@@ -11,8 +11,11 @@
 //       blend fragments; per-chunk partials of dF and dA are written out.
 //   smpl_pose_bwd_kernel  : lane = (body, joint): sums the chunk partials, back-propagates through rest-pose removal
 //       and the kinematic chain (children -> parents by depth with wave shuffles), the joint regression and the pose
-//       feature, and emits dbetas [B,10] and drotmats [B,24,3,3].
+//       feature, and emits dbetas [B,10] and drotmats [B,24,3,3].  Its AA = true instantiation (straps_smpl_bwd_aa) also reads the axis-angle
+//       pose the rotations were made from and writes d axis-angle [B,72] through the derivative of rodrigues.h (the one rodrigues_bwd_kernel uses):
+//       the same bits as straps_smpl_bwd followed by straps_rodrigues_bwd, without the drotmats round trip.
 #include "common.h"
+#include "rodrigues.h"
 
 namespace {
 
@@ -240,11 +243,14 @@ __global__ __launch_bounds__(256, 1) STRAPS_NO_PACKED_FP32 void smpl_verts_bwd_k
 // compared on the disassembly).
 // (a lane exchange of the kernel below: ds_bpermute_b32, several in flight, waits placed by the compiler)
 __device__ __forceinline__ float lane_get(float value, int src) { return __shfl(value, src, 64); }
+// (AA: compile-time flag of the fused axis-angle epilogue, no runtime branch added.  AA = false is straps_smpl_bwd's kernel: the same arithmetic, bit-identical
+//  results; as a template instantiation the compiler unrolls the dbeta shuffle loop, same speed -- DESIGN, "Axis-angle gradients")
+template <bool AA>
 __global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void smpl_pose_bwd_kernel(straps_smpl_model_t m, const float* __restrict__ betas,
                                                             const float* __restrict__ rotmats, const float* __restrict__ dFp,
                                                             const float* __restrict__ dAp, const float* __restrict__ djoints,
                                                             float* __restrict__ dbetas, float* __restrict__ drot, long long B,
-                                                            int chunks) {
+                                                            int chunks, const float* __restrict__ aa, float* __restrict__ daa) {
     const int lane = threadIdx.x & 63;
     const int j = lane & 31;
     const int base = lane & 32;
@@ -385,8 +391,17 @@ __global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void smpl_pose_bwd_kerne
             }
             if (j < 10) gbeta_direct += p[1 + j];
         }
+        if (!AA || drot) {      // (straps_smpl_bwd_aa: drotmats may be NULL)
 #pragma unroll
-        for (int e = 0; e < 9; ++e) drot[(body * 24 + j) * 9 + e] = gR[e];
+            for (int e = 0; e < 9; ++e) drot[(body * 24 + j) * 9 + e] = gR[e];
+        }
+        if constexpr (AA) {      // d axis-angle of this (body, joint): full_pose_aa / dfull_pose_aa [B][24][3]
+            float ox, oy, oz;
+            const float* r = aa + (body * 24 + j) * 3;
+            straps_rodrigues_bwd_one(r[0], r[1], r[2], gR, ox, oy, oz);
+            float* o = daa + (body * 24 + j) * 3;
+            o[0] = ox; o[1] = oy; o[2] = oz;
+        }
     }
     // dbeta[l] = dF[1+l] + sum_j sum_c Js[j][c][l] * gJ_j[c]
 #pragma unroll
@@ -418,13 +433,12 @@ extern "C" size_t straps_smpl_bwd_workspace_bytes(long long batch, int chunks) {
     return (size_t)batch * (size_t)(KP + 288 + nch * (KP + 288)) * sizeof(float);
 }
 
-extern "C" int straps_smpl_bwd(const straps_smpl_model_t* model, const float* betas, const float* rotmats, const float* dverts,
-                               const float* djoints, float* dbetas, float* drotmats, void* workspace, long long batch, int chunks,
-                               void* stream) {
-    STRAPS_REQUIRE(model && betas && rotmats && dbetas && drotmats && workspace, "straps_smpl_bwd: null pointer");
-    STRAPS_REQUIRE(model->blend_frag_t && model->children && model->jrt_ptr && model->dj_ptr && model->dj_code && model->dj_w,
-                   "straps_smpl_bwd: model lacks the backward tables");
-    STRAPS_REQUIRE(batch > 0, "straps_smpl_bwd: batch must be positive");
+namespace {
+// both entry points: the vertex pass, then the pose pass (AA: with the axis-angle epilogue).  Arguments checked by the callers.
+template <bool AA>
+int smpl_bwd_launch(const straps_smpl_model_t* model, const float* betas, const float* rotmats, const float* aa, const float* dverts,
+                    const float* djoints, float* dbetas, float* drotmats, float* daa, void* workspace, long long batch, int chunks,
+                    void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int rpc = resolve_rpc(batch, chunks);
     const int nch = (NROUNDS + rpc - 1) / rpc;
@@ -442,8 +456,30 @@ extern "C" int straps_smpl_bwd(const straps_smpl_model_t* model, const float* be
     STRAPS_CHECK_LAUNCH("smpl_verts_bwd_kernel");
     // (Round 5, DESIGN section 1: this kernel was the one whose results differed between two processes on one GPU.  Cause: a packed fp32 instruction with a
     //  low-half operand select the compiler had formed in it -- the kernel is compiled without packed fp32 instructions, STRAPS_NO_PACKED_FP32.)
-    hipLaunchKernelGGL(smpl_pose_bwd_kernel, dim3((unsigned)((batch * 32 + 255) / 256)), dim3(256), 0, st, *model, betas, rotmats, dFp, dAp,
-                       djoints, dbetas, drotmats, batch, nch);
+    hipLaunchKernelGGL(smpl_pose_bwd_kernel<AA>, dim3((unsigned)((batch * 32 + 255) / 256)), dim3(256), 0, st, *model, betas, rotmats, dFp, dAp,
+                       djoints, dbetas, drotmats, batch, nch, aa, daa);
     STRAPS_CHECK_LAUNCH("smpl_pose_bwd_kernel");
     return STRAPS_OK;
+}
+}  // namespace
+
+extern "C" int straps_smpl_bwd(const straps_smpl_model_t* model, const float* betas, const float* rotmats, const float* dverts,
+                               const float* djoints, float* dbetas, float* drotmats, void* workspace, long long batch, int chunks,
+                               void* stream) {
+    STRAPS_REQUIRE(model && betas && rotmats && dbetas && drotmats && workspace, "straps_smpl_bwd: null pointer");
+    STRAPS_REQUIRE(model->blend_frag_t && model->children && model->jrt_ptr && model->dj_ptr && model->dj_code && model->dj_w,
+                   "straps_smpl_bwd: model lacks the backward tables");
+    STRAPS_REQUIRE(batch > 0, "straps_smpl_bwd: batch must be positive");
+    return smpl_bwd_launch<false>(model, betas, rotmats, nullptr, dverts, djoints, dbetas, drotmats, nullptr, workspace, batch, chunks, stream);
+}
+
+extern "C" int straps_smpl_bwd_aa(const straps_smpl_model_t* model, const float* betas, const float* rotmats, const float* full_pose_aa,
+                                  const float* dverts, const float* djoints, float* dbetas, float* dfull_pose_aa, float* drotmats,
+                                  void* workspace, long long batch, int chunks, void* stream) {
+    STRAPS_REQUIRE(model && betas && rotmats && full_pose_aa && dbetas && dfull_pose_aa && workspace, "straps_smpl_bwd_aa: null pointer");
+    STRAPS_REQUIRE(model->blend_frag_t && model->children && model->jrt_ptr && model->dj_ptr && model->dj_code && model->dj_w,
+                   "straps_smpl_bwd_aa: model lacks the backward tables");
+    STRAPS_REQUIRE(batch > 0, "straps_smpl_bwd_aa: batch must be positive");
+    return smpl_bwd_launch<true>(model, betas, rotmats, full_pose_aa, dverts, djoints, dbetas, drotmats, dfull_pose_aa, workspace, batch, chunks,
+                                 stream);
 }

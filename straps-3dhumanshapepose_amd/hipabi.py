@@ -141,7 +141,7 @@ def gemm_multi(descs):
 _P, _I, _L, _F, _Z, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes); must list every symbol of include/straps_hip.h (tests/test_abi.py checks)
-ABI_VERSION = 9      # == STRAPS_ABI_VERSION of include/straps_hip.h (tests/test_abi.py compares the two); load() refuses a library of another version
+ABI_VERSION = 10     # == STRAPS_ABI_VERSION of include/straps_hip.h (tests/test_abi.py compares the two); load() refuses a library of another version
 SIGNATURES = {
     'straps_abi_version': (_I, []),
     'straps_last_error': (C.c_char_p, []),
@@ -203,6 +203,7 @@ SIGNATURES = {
     'straps_gemm_multi': (_I, [C.POINTER(GemmDesc), _I, _P]),
     'straps_rot6d_fwd': (_I, [_P, _L, _I, _P, _L, _P]),
     'straps_rodrigues_fwd': (_I, [_P, _P, _L, _P]),
+    'straps_rodrigues_bwd': (_I, [_P, _P, _P, _L, _P]),
     'straps_orthographic_project': (_I, [_P, _P, _I, _P, _L, _I, _P]),
     'straps_orthographic_project_bwd': (_I, [_P, _P, _I, _P, _P, _P, _L, _I, _P]),
     'straps_perspective_project': (_I, [_P, _P, _P, _P, _I, _P, _L, _I, _P]),
@@ -210,6 +211,8 @@ SIGNATURES = {
     'straps_smpl_fwd': (_I, [C.POINTER(SmplModelStruct), _P, _P, _P, _P, _P, _L, _I, _I, _P]),
     'straps_smpl_bwd_workspace_bytes': (_Z, [_L, _I]),
     'straps_smpl_bwd': (_I, [C.POINTER(SmplModelStruct), _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
+    # axis-angle gradients (ABI 10)
+    'straps_smpl_bwd_aa': (_I, [C.POINTER(SmplModelStruct), _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
     'straps_conv_dgrad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'straps_conv_wgrad_workspace_bytes': (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
     'straps_conv_wgrad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

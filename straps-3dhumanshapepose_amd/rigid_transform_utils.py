@@ -29,9 +29,19 @@ def _rot6d_fwd(x):
 
 
 def batch_rodrigues(rot_vecs):
-    """axis-angle [N,3] -> [N,3,3] with smplx's convention angle = ||r + 1e-8||."""
+    """axis-angle [N,3] -> [N,3,3] with smplx's convention angle = ||r + 1e-8||.  Differentiable like smplx's: an input that
+    requires grad (with grad enabled) gets its gradient from straps_rodrigues_bwd."""
     hipabi.require_gpu_tensor(rot_vecs, 'axis-angle input', torch.float32)
-    r = rot_vecs.detach().contiguous().view(-1, 3)
+    if torch.is_grad_enabled() and rot_vecs.requires_grad:
+        from .autograd_ops import rodrigues_autograd
+        return rodrigues_autograd(rot_vecs)
+    return _rodrigues_fwd(rot_vecs.detach())
+
+
+def _rodrigues_fwd(rot_vecs):
+    # (checked here as well: every launch of the kernel goes through this function, _SmplAaFn's included)
+    hipabi.require_gpu_tensor(rot_vecs, 'axis-angle input', torch.float32)
+    r = rot_vecs.contiguous().view(-1, 3)
     out = torch.empty(r.shape[0], 3, 3, device=r.device, dtype=torch.float32)
     hipabi.check(hipabi.lib().straps_rodrigues_fwd(hipabi.ptr(r), hipabi.ptr(out), r.shape[0], hipabi.stream_ptr()),
                  'straps_rodrigues_fwd')

@@ -270,16 +270,22 @@ class SMPL(nn.Module):
         if pose2rot:
             full_pose = torch.cat([global_orient.reshape(-1, 3).expand(B, -1) if global_orient.shape[0] != B
                                    else global_orient.reshape(B, 3), body_pose.reshape(body_pose.shape[0], -1).expand(B, -1)],
-                                  dim=1).detach()
-            rotmats = batch_rodrigues(full_pose.reshape(-1, 3)).view(B, 24, 3, 3)
+                                  dim=1)
+            if torch.is_grad_enabled() and (betas.requires_grad or full_pose.requires_grad):
+                # axis-angle gradients flow as through smplx (autograd sums a broadcast global_orient / body_pose over the batch)
+                from .autograd_ops import smpl_aa_forward_autograd
+                verts, joints = smpl_aa_forward_autograd(self, betas, full_pose)
+            else:
+                rotmats = batch_rodrigues(full_pose.detach().reshape(-1, 3)).view(B, 24, 3, 3)
+                verts, joints = self.forward_arrays(betas.detach().float(), rotmats)
         else:
             full_pose = torch.cat([global_orient.reshape(-1, 1, 3, 3), body_pose.reshape(-1, 23, 3, 3)], dim=1)
             rotmats = full_pose
-        if torch.is_grad_enabled() and (betas.requires_grad or rotmats.requires_grad):
-            from .autograd_ops import smpl_forward_autograd
-            verts, joints = smpl_forward_autograd(self, betas, rotmats)
-        else:
-            verts, joints = self.forward_arrays(betas.detach().float(), rotmats.detach().float())
+            if torch.is_grad_enabled() and (betas.requires_grad or rotmats.requires_grad):
+                from .autograd_ops import smpl_forward_autograd
+                verts, joints = smpl_forward_autograd(self, betas, rotmats)
+            else:
+                verts, joints = self.forward_arrays(betas.detach().float(), rotmats.detach().float())
         tr = self.transl if transl is None else transl
         if transl is not None:          # module default is zeros: skip the add
             verts = verts + tr[:, None]
