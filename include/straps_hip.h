@@ -9,7 +9,10 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); nothing synchronises;
  *   - no hidden allocation: outputs and workspaces are caller-owned, sizes given by *_bytes();
  *   - return value: 0 = STRAPS_OK, otherwise an error code; straps_last_error() gives the text;
- *   - all arithmetic is IEEE fp32 (fp32-input MFMA = exact fmaf chains; no reduced precision);
+ *   - every tensor at the boundary is fp32.  Arithmetic: fp32 everywhere, except where an entry point
+ *     says otherwise -- the bf16x3 convolutions (operands split into three exact bf16 planes, six
+ *     products per term on the bf16 matrix pipe, fp32 accumulate: the fp32 chain's accuracy class) and
+ *     the fp16x3 SMPL modes.  The fp32 routes use fp32-input MFMA (exact fmaf chains);
  *   - activations inside the encoder are NHWC fp32; the boundary tensor (network input) is NCHW
  *     exactly as the reference passes it (models/regressor.py:43).
  */
@@ -23,7 +26,7 @@
 extern "C" {
 #endif
 
-#define STRAPS_ABI_VERSION 10
+#define STRAPS_ABI_VERSION 11
 
 #define STRAPS_OK 0
 #define STRAPS_EINVAL 1       /* bad argument (shape, alignment, null pointer) */
@@ -727,6 +730,46 @@ int straps_point_metrics(const float* pred, const float* target, float* out3, lo
 int straps_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                      long long n, int step, float lr, float beta1, float beta2, float eps,
                      float grad_scale, const long long* step_dev, void* stream);
+
+/* ---- the whole eval-mode regressor in one call (ABI 11; csrc/regressor.hip) -----------------------------------------------------
+ * proxy representation -> (camera, pose, shape), models/regressor.py:43-47 under .eval(): the encoder with BatchNorm on its running
+ * statistics, then the IEF iterations.  Inference only (no gradients).  The launches are those SingleInputRegressor.eval() makes, with
+ * the same arguments (same convolution routes, tile_cfg 0), so the results are bit-identical to the module's.
+ *
+ * desc: layers 18 | 50; in_channels 1..256; ief_iters 1..64; precision 0 = bf16x3 (ResNet's default conv_precision) | 1 = fp32.
+ *
+ * params: ONE flat fp32 device buffer of straps_regressor_param_floats() floats: every tensor of the regressor's state_dict(), in
+ *   its order, flattened row-major, WITHOUT the `num_batches_tracked` entries and WITHOUT the `ief_module.ief_layers.*` aliases of
+ *   fc1/fc2/fc3; then the IEF's initial estimate (157 floats: 0.9, 0, 0, mean 6-D pose, mean shape), which is an attribute, not a
+ *   state-dict entry.  That is, for resnet18:
+ *     image_encoder.conv1.weight [64][in_channels][7][7], image_encoder.bn1.{weight, bias, running_mean, running_var} [64],
+ *     per unit (layer1.0, layer1.1, ..., layer4.last): conv1.weight, bn1.{4}, conv2.weight, bn2.{4}, (resnet50: conv3.weight, bn3.{4}),
+ *       then downsample.0.weight, downsample.1.{4} where the unit has a projection,
+ *     ief_module.fc1.weight [h][f + 157], fc1.bias [h], fc2.weight [h][h], fc2.bias [h], fc3.weight [157][h], fc3.bias [157],
+ *     initial estimate [157]                                      (f, h = 512, 512 for resnet18; 2048, 1024 for resnet50).
+ *   BatchNorm eps is 1e-5 (nn.BatchNorm2d's default).
+ * straps_regressor_prepare: params -> the prepared buffer (straps_regressor_prepared_bytes, 256-byte aligned): folded BatchNorm,
+ *   the stem's fragment-order weights, the convolution weights packed for `precision` (bf16x3 planes / KRSC fp32), the IEF packing and
+ *   copies of the IEF's other tensors.  It synchronises `stream` before returning; afterwards neither `params` nor host memory is
+ *   read.  The prepared buffer does not depend on the batch or the image size.
+ * straps_regressor_workspace_bytes: scratch of straps_regressor_fwd_infer for this (batch, h, w) -- a fixed set of slots reused by
+ *   every layer, not a sum over layers; 0 for an invalid request.
+ * straps_regressor_fwd_infer: x NCHW [batch][in_channels][h][w] -> est [batch][ld_est] (ld_est >= 157: cam 3 | pose 144 | shape 10)
+ *   and, if rotmats != NULL, rotmats [batch][24][3][3] = straps_rot6d_fwd of the pose columns.  Everything is enqueued on `stream`:
+ *   nothing synchronises or allocates, so the call can be captured into a hipGraph.  workspace (256-byte aligned) of at least
+ *   straps_regressor_workspace_bytes(desc, batch, h, w) bytes, checked before any launch; its content on entry does not matter. */
+typedef struct {
+    int layers;        /* 18 | 50 */
+    int in_channels;   /* >= 1 (reference: 1 or 18) */
+    int ief_iters;     /* >= 1 (reference: 3) */
+    int precision;     /* 0 = bf16x3, 1 = fp32 */
+} straps_regressor_desc_t;
+size_t straps_regressor_param_floats(const straps_regressor_desc_t* desc);
+size_t straps_regressor_prepared_bytes(const straps_regressor_desc_t* desc);
+int straps_regressor_prepare(const straps_regressor_desc_t* desc, const float* params, void* prepared, void* stream);
+size_t straps_regressor_workspace_bytes(const straps_regressor_desc_t* desc, int batch, int h, int w);
+int straps_regressor_fwd_infer(const straps_regressor_desc_t* desc, const void* prepared, const float* x, int batch, int h, int w,
+                               float* est, int ld_est, float* rotmats, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- gradient exchange of data-parallel training -----------------------------------------------
  * The reference trains on one GPU (run_train.py:23-26) and so has no counterpart; north_star asks for "a single RCCL all-reduce of

@@ -10,6 +10,7 @@ from .synthetic_smpl import synthetic_smpl_model, synthetic_mean_params, load_sm
 from .resnet import ResNet, BasicBlock, Bottleneck, resnet18, resnet50  # noqa: F401
 from .ief_module import IEFModule  # noqa: F401
 from .regressor import SingleInputRegressor  # noqa: F401
+from .infer import InferenceRegressor, flat_inference_params  # noqa: F401
 from .smpl import SMPL, ModelOutput, pack_smpl_model  # noqa: F401
 from .rigid_transform_utils import rot6d_to_rotmat, batch_rodrigues  # noqa: F401
 from .multi_task_loss import HomoscedasticUncertaintyWeightedMultiTaskLoss  # noqa: F401

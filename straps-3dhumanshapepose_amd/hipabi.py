@@ -13,7 +13,8 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'smpl.hip',
-           'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip']
+           'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
+           'regressor.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -138,10 +139,15 @@ def gemm_multi(descs):
     check(lib().straps_gemm_multi(arr, len(descs), stream_ptr()), 'straps_gemm_multi')
 
 
+class RegressorDesc(C.Structure):
+    """mirror of straps_regressor_desc_t"""
+    _fields_ = [('layers', C.c_int32), ('in_channels', C.c_int32), ('ief_iters', C.c_int32), ('precision', C.c_int32)]
+
+
 _P, _I, _L, _F, _Z, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes); must list every symbol of include/straps_hip.h (tests/test_abi.py checks)
-ABI_VERSION = 10     # == STRAPS_ABI_VERSION of include/straps_hip.h (tests/test_abi.py compares the two); load() refuses a library of another version
+ABI_VERSION = 11     # == STRAPS_ABI_VERSION of include/straps_hip.h (tests/test_abi.py compares the two); load() refuses a library of another version
 SIGNATURES = {
     'straps_abi_version': (_I, []),
     'straps_last_error': (C.c_char_p, []),
@@ -261,6 +267,12 @@ SIGNATURES = {
     'straps_comm_size': (_I, [_P]),
     'straps_comm_library': (C.c_char_p, []),
     'straps_allreduce_grads': (_I, [_P, _L, _P, _P]),
+    # the whole eval-mode regressor in one call (ABI 11)
+    'straps_regressor_param_floats': (_Z, [C.POINTER(RegressorDesc)]),
+    'straps_regressor_prepared_bytes': (_Z, [C.POINTER(RegressorDesc)]),
+    'straps_regressor_prepare': (_I, [C.POINTER(RegressorDesc), _P, _P, _P]),
+    'straps_regressor_workspace_bytes': (_Z, [C.POINTER(RegressorDesc), _I, _I, _I]),
+    'straps_regressor_fwd_infer': (_I, [C.POINTER(RegressorDesc), _P, _P, _I, _I, _I, _P, _I, _P, _P, _Z, _P]),
 }
 
 
