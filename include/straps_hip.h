@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define STRAPS_ABI_VERSION 11
+#define STRAPS_ABI_VERSION 12
 
 #define STRAPS_OK 0
 #define STRAPS_EINVAL 1       /* bad argument (shape, alignment, null pointer) */
@@ -521,11 +521,21 @@ size_t straps_conv_wgrad_workspace_bytes(int batch, int h, int w, int cin, int c
 int straps_conv_wgrad(const float* x_nhwc, const float* dy_nhwc, float* dw_oihw, void* workspace,
                       int batch, int h, int w, int cin, int cout, int kh, int kw, int stride,
                       int pad, int accumulate, void* stream);
-/* stem weight gradient straight from the NCHW input (the input itself needs no gradient).        */
+/* stem weight gradient straight from the NCHW input (its data gradient: straps_stem_dgrad below). */
 size_t straps_stem_wgrad_workspace_bytes(int batch, int cin, int h, int w);
 int straps_stem_wgrad(const float* x_nchw, const float* dy_nhwc, float* dw_oihw, void* workspace,
                       const uint32_t* nzmask /* optional, see straps_stem_fwd */, int batch, int cin,
                       int h, int w, int accumulate, void* stream);
+/* stem data gradient (gradient w.r.t. the network input): dx_nchw [batch][cin][h][w] (+)= the gradient of the 7x7 / stride 2 /
+ * pad 3 convolution given dy_nhwc [batch][Ho][Wo][64] (Ho = (h-1)/2 + 1, the raw-output gradient the BatchNorm backward writes)
+ * and the weight packed by straps_pack_stem_dgrad_weight (straps_stem_dgrad_weight_floats(cin) floats) from OIHW [64][cin][7][7].
+ * Dense (no zero skipping); exact fp32 products with fp32 accumulation on the fp32 matrix pipe.  h, w >= 7 (odd sizes allowed),
+ * 1 <= cin <= STRAPS_STEM_DGRAD_MAX_CIN, accumulate = 0 (overwrite) or 1 (add).  weight_floats returns 0 for an unsupported cin. */
+#define STRAPS_STEM_DGRAD_MAX_CIN 64
+size_t straps_stem_dgrad_weight_floats(int cin);
+int straps_pack_stem_dgrad_weight(const float* w_oihw, float* w_pk, int cin, void* stream);
+int straps_stem_dgrad(const float* dy_nhwc, const float* w_pk, float* dx_nchw, int batch, int cin, int h, int w,
+                      int accumulate, void* stream);
 /* training-mode BatchNorm backward with the ReLU mask fused: dz = dy * (yact > 0) (yact NULL = no
  * ReLU), dgamma/dbeta, draw = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)); dz_out (optional,
  * may alias dy) receives dz for the skip connection.  When the activation was exactly

@@ -228,11 +228,14 @@ def _conv_dgrad(L, net, rec, draw, addend, planes_sink=None, bn_next=None, adden
     return dx
 
 
-def encoder_backward(net, tape, dfeat, views=None, side_stream=None, after_layer3=None):
+def encoder_backward(net, tape, dfeat, views=None, side_stream=None, after_layer3=None, want_dx=False, param_grads=True):
     """tape: dict filled by encoder_forward(net, x, tape) in training mode.  Returns {param: grad}.
     side_stream: optional second torch stream for the weight-gradient kernels (joined before returning).
     after_layer3: optional callback run once the gradients of layer4 and layer3 (78 % / 94 % of resnet18 / 50's parameters)
-    are final on the current stream -- the training step starts their all-reduce there (and switches hipGraphs)."""
+    are final on the current stream -- the training step starts their all-reduce there (and switches hipGraphs).
+    want_dx: also compute the gradient w.r.t. the NCHW input (straps_stem_dgrad) and return ({param: grad}, dx).
+    param_grads=False: no convolution / stem weight gradient is launched (nothing needs one); the BatchNorm sums still run (the data
+    gradient needs them) and their dgamma / dbeta land in the returned dict."""
     L = hipabi.lib()
     grads = GradSink(views)
     side = _SideStream(side_stream)
@@ -265,11 +268,13 @@ def encoder_backward(net, tape, dfeat, views=None, side_stream=None, after_layer
                 dz = dy
             else:
                 draw, dz = _bn_bwd(L, rec, dy, True, True, grads, sink_of(rec), keep(rec))    # ReLU(out) mask; dz feeds the skip connection
-            side.run(lambda rec=rec, draw=draw: _conv_wgrad(L, rec, draw, grads, sink), draw)
+            if param_grads:
+                side.run(lambda rec=rec, draw=draw: _conv_wgrad(L, rec, draw, grads, sink), draw)
             if unit.downsample is not None:
                 recd = tape[id(unit.downsample[0])]
                 drawd, _ = _bn_bwd(L, recd, dz, False, False, grads, sink_of(recd), keep(recd), mask_bits=ubits)
-                side.run(lambda recd=recd, drawd=drawd: _conv_wgrad(L, recd, drawd, grads, sink), drawd)
+                if param_grads:
+                    side.run(lambda recd=recd, drawd=drawd: _conv_wgrad(L, recd, drawd, grads, sink), drawd)
                 dskip = _conv_dgrad(L, net, recd, drawd, None, sink)
             else:
                 dskip, dskip_bits = dz, ubits
@@ -278,7 +283,8 @@ def encoder_backward(net, tape, dfeat, views=None, side_stream=None, after_layer
                 dt = _conv_dgrad(L, net, tape[id(pairs[ci][0])], draw, None, sink, bn_next=rec_prev if sink is not None else None)
                 rec = rec_prev
                 draw, _ = _bn_bwd(L, rec, dt, True, False, grads, sink_of(rec), keep(rec))
-                side.run(lambda rec=rec, draw=draw: _conv_wgrad(L, rec, draw, grads, sink), draw)
+                if param_grads:
+                    side.run(lambda rec=rec, draw=draw: _conv_wgrad(L, rec, draw, grads, sink), draw)
             # (+ skip gradient fused in the epilogue; the result is dy of the PREVIOUS unit's last BatchNorm, whose sums ride along)
             dy = _conv_dgrad(L, net, tape[id(pairs[0][0])], draw, dskip, sink, bn_next=prev_last if sink is not None else None,
                              addend_bits=dskip_bits)
@@ -295,9 +301,10 @@ def encoder_backward(net, tape, dfeat, views=None, side_stream=None, after_layer
         ws = torch.empty(L.straps_bn_bwd_workspace_bytes(B * H * W, Cc) // 4, device=raw.device, dtype=torch.float32)
         dgamma, dbeta = grads.buf(bn.weight), grads.buf(bn.bias)
         draw = _empty_like(raw)
-        # the stem weight gradient -- draw's only reader -- skips the tiles with no non-zero input under them: they stay unwritten
+        # the stem weight gradient -- draw's only reader unless the input's gradient is wanted -- skips the tiles with no non-zero input
+        # under them: they stay unwritten.  The data gradient reads every tile: draw is then dense (the weight gradient's skipping stays)
         tact = None
-        if rec.get('nzmask') is not None and _SPARSE_STEM_TAIL:
+        if rec.get('nzmask') is not None and _SPARSE_STEM_TAIL and not want_dx:
             _, Cin0, Hin, Win = rec['geom'][:4]
             tact = torch.empty(L.straps_stem_tiles(B, Hin, Win), device=raw.device, dtype=torch.uint8)
             hipabi.check(L.straps_stem_tile_activity(hipabi.ptr(rec['nzmask']), hipabi.ptr(tact), B, Cin0, Hin, Win, hipabi.stream_ptr()),
@@ -315,18 +322,24 @@ def encoder_backward(net, tape, dfeat, views=None, side_stream=None, after_layer
         rec = tape['stem']
         draw, _ = _bn_bwd(L, rec, dstem, True, False, grads)
     B, Cin, H, W, Ho, Wo = rec['geom']
-    ws = torch.empty(L.straps_stem_wgrad_workspace_bytes(B, Cin, H, W) // 4, device=draw.device, dtype=torch.float32)
-    dw = grads.buf(net.conv1.weight)
-    hipabi.check(L.straps_stem_wgrad(hipabi.ptr(rec['x']), hipabi.ptr(draw), hipabi.ptr(dw), hipabi.ptr(ws), hipabi.ptr(rec.get('nzmask')),
-                                     B, Cin, H, W, 0, hipabi.stream_ptr()), 'straps_stem_wgrad')
-    grads[net.conv1.weight] = dw
+    dx = None
+    if want_dx:
+        dx = torch.empty(B, Cin, H, W, device=draw.device, dtype=torch.float32)
+        hipabi.check(L.straps_stem_dgrad(hipabi.ptr(draw), hipabi.ptr(net._packed_stem_dgrad_weight()), hipabi.ptr(dx), B, Cin, H, W, 0,
+                                         hipabi.stream_ptr()), 'straps_stem_dgrad')
+    if param_grads:
+        ws = torch.empty(L.straps_stem_wgrad_workspace_bytes(B, Cin, H, W) // 4, device=draw.device, dtype=torch.float32)
+        dw = grads.buf(net.conv1.weight)
+        hipabi.check(L.straps_stem_wgrad(hipabi.ptr(rec['x']), hipabi.ptr(draw), hipabi.ptr(dw), hipabi.ptr(ws), hipabi.ptr(rec.get('nzmask')),
+                                         B, Cin, H, W, 0, hipabi.stream_ptr()), 'straps_stem_wgrad')
+        grads[net.conv1.weight] = dw
     side.join()
-    return grads
+    return (grads, dx) if want_dx else grads
 
 
 # ------------------------------------------------------------------------------------------ IEF
-def ief_backward(ief, feat, tape, dest, views=None):
-    """dest: gradient w.r.t. the final estimate [B,160].  Returns (dfeat, {param: grad}).
+def ief_backward(ief, feat, tape, dest, views=None, param_grads=True):
+    """dest: gradient w.r.t. the final estimate [B,160].  Returns (dfeat, {param: grad}); param_grads=False: dfeat only ({}).
     Launches: one copy of dest into its slot, three small GEMMs per iteration (the dependent chain: ReLU masks, the `est_out = est_in + ...`
     addend and the running sum dc1 fused into their epilogues), then ONE launch with every weight / bias gradient and the feature
     gradient -- a weight gradient is a single GEMM over the three iterations' stacked rows (K = 3 B), a bias gradient the same against
@@ -359,6 +372,9 @@ def ief_backward(ief, feat, tape, dest, views=None):
         hipabi.gemm_multi([D(dh1s[it], H1, 1, pk['w1e'], EST_LD, 1, dests[it], EST_LD, B, P, H1, addend=dests[it + 1], ldadd=EST_LD)])
     one = pk['one']
     dfeat = e(B, F)
+    if not param_grads:     # (the same GEMM as in the launch below: a problem's arithmetic does not depend on its neighbours)
+        hipabi.gemm_multi([D(dc1, H1, 1, pk['w1f'], F, 1, dfeat, F, B, F, H1)])
+        return dfeat, {}
     KB = T * B
     hipabi.gemm_multi([
         D(dh2s, 1, H2, h1s, H1, 1, dW2, H1, H2, H1, KB),                                                  # dW2 = sum_it dh2^T h1
@@ -389,12 +405,14 @@ class _RegressorFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dest):
         reg = ctx.reg
-        dfeat, g_ief = ief_backward(reg.ief_module, ctx.feat, ctx.ief_tape, dest)
-        g_enc = encoder_backward(reg.image_encoder, ctx.enc_tape, dfeat)
+        want_dx, pg = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        dfeat, g_ief = ief_backward(reg.ief_module, ctx.feat, ctx.ief_tape, dest, param_grads=pg)
+        g_enc = encoder_backward(reg.image_encoder, ctx.enc_tape, dfeat, want_dx=want_dx, param_grads=pg)
+        g_enc, dx = g_enc if want_dx else (g_enc, None)
         g_enc.update(g_ief)
-        out = [g_enc.get(p) if p.requires_grad else None for p in ctx.params]
+        out = [g_enc.get(p) if need else None for p, need in zip(ctx.params, ctx.needs_input_grad[2:])]
         ctx.enc_tape = ctx.ief_tape = None
-        return (None, None) + tuple(out)
+        return (None, dx) + tuple(out)
 
 
 def regressor_autograd(reg, x):
@@ -404,6 +422,32 @@ def regressor_autograd(reg, x):
     est = _RegressorFn.apply(reg, x, *params)
     P = reg.ief_module.num_output_params
     return est[:, :3], est[:, 3:3 + 24 * 6], est[:, 3 + 24 * 6:P]
+
+
+class _EncoderFn(torch.autograd.Function):
+    """input [B,C,H,W] -> features [B,F]: the taped encoder_forward _RegressorFn runs (same launches, same bits), encoder_backward
+    for the input and parameter gradients -- ResNet.forward in grad mode, so the encoder trains or fine-tunes as a module of its own."""
+
+    @staticmethod
+    def forward(ctx, net, x, *params):
+        tape = {}
+        with torch.no_grad():
+            feat = encoder_forward(net, x, tape)
+        ctx.net, ctx.tape, ctx.params = net, tape, params
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        want_dx = ctx.needs_input_grad[1]
+        g = encoder_backward(ctx.net, ctx.tape, dfeat, want_dx=want_dx, param_grads=any(ctx.needs_input_grad[2:]))
+        g, dx = g if want_dx else (g, None)
+        ctx.tape = None
+        return (None, dx) + tuple(g.get(p) if need else None for p, need in zip(ctx.params, ctx.needs_input_grad[2:]))
+
+
+def encoder_autograd(net, x):
+    hipabi.require_gpu_tensor(x, 'encoder input', torch.float32)
+    return _EncoderFn.apply(net, x, *list(net.parameters()))
 
 
 class _IefFn(torch.autograd.Function):
@@ -417,8 +461,8 @@ class _IefFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dest):
-        dfeat, g = ief_backward(ctx.ief, ctx.feat, ctx.tape, dest)
-        return (None, dfeat) + tuple(g.get(p) if p.requires_grad else None for p in ctx.params)
+        dfeat, g = ief_backward(ctx.ief, ctx.feat, ctx.tape, dest, param_grads=any(ctx.needs_input_grad[2:]))
+        return (None, dfeat) + tuple(g.get(p) if need else None for p, need in zip(ctx.params, ctx.needs_input_grad[2:]))
 
 
 def ief_autograd(ief, feat):

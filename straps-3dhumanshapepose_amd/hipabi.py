@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
-SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'smpl.hip',
+SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
            'regressor.hip']
 
@@ -147,7 +147,7 @@ class RegressorDesc(C.Structure):
 _P, _I, _L, _F, _Z, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes); must list every symbol of include/straps_hip.h (tests/test_abi.py checks)
-ABI_VERSION = 11     # == STRAPS_ABI_VERSION of include/straps_hip.h (tests/test_abi.py compares the two); load() refuses a library of another version
+ABI_VERSION = 12     # == STRAPS_ABI_VERSION of include/straps_hip.h (tests/test_abi.py compares the two); load() refuses a library of another version
 SIGNATURES = {
     'straps_abi_version': (_I, []),
     'straps_last_error': (C.c_char_p, []),
@@ -224,6 +224,9 @@ SIGNATURES = {
     'straps_conv_wgrad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'straps_stem_wgrad_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     'straps_stem_wgrad': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'straps_stem_dgrad_weight_floats': (_Z, [_I]),
+    'straps_pack_stem_dgrad_weight': (_I, [_P, _P, _I, _P]),
+    'straps_stem_dgrad': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'straps_bn_bwd_blocks': (_I, [_L, _I]),
     'straps_bn_bwd_workspace_bytes': (_Z, [_L, _I]),
     'straps_bn_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),

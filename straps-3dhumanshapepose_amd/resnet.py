@@ -279,8 +279,25 @@ class ResNet(nn.Module):
             return ss
         return self._cached(('bnf', id(bn)), [bn.weight, bn.bias, bn.running_mean, bn.running_var], make, extra=(self._bn_epoch,))
 
+    def _packed_stem_dgrad_weight(self):
+        """conv1.weight in the [K][N] fragment order of the stem data gradient (straps_pack_stem_dgrad_weight)"""
+        w = self.conv1.weight
+        L = hipabi.lib()
+
+        def make():
+            wd = w.detach().contiguous()
+            out = torch.empty(L.straps_stem_dgrad_weight_floats(wd.shape[1]), device=wd.device, dtype=torch.float32)
+            hipabi.check(L.straps_pack_stem_dgrad_weight(hipabi.ptr(wd), hipabi.ptr(out), wd.shape[1], hipabi.stream_ptr()),
+                         'straps_pack_stem_dgrad_weight')
+            return out
+        return self._cached(('wsd', id(self.conv1)), [w], make)
+
     @hipabi.on_tensor_device
     def forward(self, x):
+        # grad mode with anything to differentiate: the taped forward + encoder_backward (input and parameter gradients)
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            from .autograd_ops import encoder_autograd
+            return encoder_autograd(self, x)
         from .encoder_exec import encoder_forward
         return encoder_forward(self, x)
 
