@@ -781,6 +781,47 @@ size_t straps_regressor_workspace_bytes(const straps_regressor_desc_t* desc, int
 int straps_regressor_fwd_infer(const straps_regressor_desc_t* desc, const void* prepared, const float* x, int batch, int h, int w,
                                float* est, int ld_est, float* rotmats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the train-mode regressor forward and backward (added without a version change; csrc/regressor_train.hip) ---------------------
+ * models/regressor.py:43-47 under .train(), differentiated: what SingleInputRegressor's autograd path computes for reg.train(); reg(x);
+ * torch.autograd.backward(...), with the module's defaults.  The launches are those the module makes, with the same arguments (same
+ * convolution routes, ReLU bits, fused stem tail, tile_cfg 0, weight-gradient splits, batched IEF backward), so the estimate, every
+ * gradient and the running statistics are bit-identical to the module's.  desc as above.
+ *
+ * params: straps_regressor_train_param_floats() floats, exactly torch.cat([p.reshape(-1) for p in regressor.parameters()]):
+ *   image_encoder.conv1.weight, bn1.{weight, bias}, per unit conv1.weight, bn1.{weight, bias}, conv2 ..., (resnet50: conv3 ...), then
+ *   downsample.0.weight, downsample.1.{weight, bias} where the unit has a projection, then ief_module.fc1.{weight, bias}, fc2.{...},
+ *   fc3.{...}.  The library never writes it; it is the first part of a training step's flat parameter buffer, so straps_adam_step
+ *   runs over it unchanged.
+ * bn_state: straps_regressor_bn_state_floats() floats, running_mean then running_var of every BatchNorm in module order (bn1, then
+ *   per unit bn1, bn2, (bn3), downsample.1).  fwd_train updates it in place as nn.BatchNorm2d does in train mode (momentum 0.1,
+ *   eps 1e-5, the unbiased batch variance in the running value).  num_batches_tracked belongs to the host.
+ * init_est: the IEF's initial estimate, 157 floats.
+ * straps_regressor_train_workspace_bytes: the tape (every layer's raw output, statistics, the activations the backward reads, the
+ *   IEF's per-iteration activations, the packed weights) plus the backward's scratch, for this (batch, h, w); 0 if invalid.
+ * straps_regressor_fwd_train: train-mode forward with batch statistics: x NCHW [batch][in_channels][h][w] -> est [batch][ld_est]
+ *   (ld_est >= 157).  It packs the weights for the forward and the data gradient into the workspace (one batched launch) and
+ *   records the tape there; the workspace's content on entry does not matter.
+ * straps_regressor_bwd: consumes the tape of the immediately preceding fwd_train on the same workspace; `params` and `x` must be
+ *   unchanged in between (the caller's contract: it cannot be checked).  dest [batch][ld_dest] (ld_dest >= 157; columns 157 and
+ *   above are not read) is the gradient w.r.t. est.  grads (layout of `params`) is OVERWRITTEN, not accumulated; grads == NULL runs
+ *   no weight-gradient kernel.  dx != NULL receives the NCHW input gradient (straps_stem_dgrad: in_channels <= 64); asking for it
+ *   makes the stem tail's gradient dense, so the stem weight gradient reads every tile.
+ * straps_regressor_export_infer_params: params + bn_state + init_est -> the straps_regressor_param_floats() layout of
+ *   straps_regressor_prepare (device-to-device copies on `stream`).
+ * None of them synchronises or allocates: a fwd_train + bwd pair can be captured into one hipGraph.  Every argument is checked
+ * before any HIP call (STRAPS_EINVAL, straps_last_error() names the field).                                                        */
+size_t straps_regressor_train_param_floats(const straps_regressor_desc_t* desc);
+size_t straps_regressor_bn_state_floats(const straps_regressor_desc_t* desc);
+size_t straps_regressor_train_workspace_bytes(const straps_regressor_desc_t* desc, int batch, int h, int w);
+int straps_regressor_fwd_train(const straps_regressor_desc_t* desc, const float* params, float* bn_state, const float* init_est,
+                               const float* x, int batch, int h, int w, float* est, int ld_est,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int straps_regressor_bwd(const straps_regressor_desc_t* desc, const float* params, const float* x, int batch, int h, int w,
+                         const float* dest, int ld_dest, float* grads, float* dx,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int straps_regressor_export_infer_params(const straps_regressor_desc_t* desc, const float* params, const float* bn_state,
+                                         const float* init_est, float* infer_params, void* stream);
+
 /* ---- gradient exchange of data-parallel training -----------------------------------------------
  * The reference trains on one GPU (run_train.py:23-26) and so has no counterpart; north_star asks for "a single RCCL all-reduce of
  * grads over xGMI per step".  These entry points give a host WITHOUT torch that exchange: the flat fp32 gradient buffer every

@@ -11,6 +11,7 @@ from .resnet import ResNet, BasicBlock, Bottleneck, resnet18, resnet50  # noqa: 
 from .ief_module import IEFModule  # noqa: F401
 from .regressor import SingleInputRegressor  # noqa: F401
 from .infer import InferenceRegressor, flat_inference_params  # noqa: F401
+from .train_abi import CompositeTrainer, flat_training_params, flat_bn_state  # noqa: F401
 from .smpl import SMPL, ModelOutput, pack_smpl_model  # noqa: F401
 from .rigid_transform_utils import rot6d_to_rotmat, batch_rodrigues  # noqa: F401
 from .multi_task_loss import HomoscedasticUncertaintyWeightedMultiTaskLoss  # noqa: F401

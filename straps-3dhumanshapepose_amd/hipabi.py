@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
-           'regressor.hip']
+           'regressor.hip', 'regressor_train.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -276,6 +276,13 @@ SIGNATURES = {
     'straps_regressor_prepare': (_I, [C.POINTER(RegressorDesc), _P, _P, _P]),
     'straps_regressor_workspace_bytes': (_Z, [C.POINTER(RegressorDesc), _I, _I, _I]),
     'straps_regressor_fwd_infer': (_I, [C.POINTER(RegressorDesc), _P, _P, _I, _I, _I, _P, _I, _P, _P, _Z, _P]),
+    # the train-mode regressor forward and backward (added without a version change)
+    'straps_regressor_train_param_floats': (_Z, [C.POINTER(RegressorDesc)]),
+    'straps_regressor_bn_state_floats': (_Z, [C.POINTER(RegressorDesc)]),
+    'straps_regressor_train_workspace_bytes': (_Z, [C.POINTER(RegressorDesc), _I, _I, _I]),
+    'straps_regressor_fwd_train': (_I, [C.POINTER(RegressorDesc), _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _Z, _P]),
+    'straps_regressor_bwd': (_I, [C.POINTER(RegressorDesc), _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _Z, _P]),
+    'straps_regressor_export_infer_params': (_I, [C.POINTER(RegressorDesc), _P, _P, _P, _P, _P]),
 }
 
 
