@@ -11,8 +11,10 @@
  *   - return value: 0 = STRAPS_OK, otherwise an error code; straps_last_error() gives the text;
  *   - every tensor at the boundary is fp32.  Arithmetic: fp32 everywhere, except where an entry point
  *     says otherwise -- the bf16x3 convolutions (operands split into three exact bf16 planes, six
- *     products per term on the bf16 matrix pipe, fp32 accumulate: the fp32 chain's accuracy class) and
- *     the fp16x3 SMPL modes.  The fp32 routes use fp32-input MFMA (exact fmaf chains);
+ *     products per term on the bf16 matrix pipe, fp32 accumulate: the fp32 chain's accuracy class), the
+ *     opt-in single-product bf16 inference route (operands rounded to bf16, one product per term, fp32
+ *     accumulate: bf16 accuracy; straps_conv_fwd_bf16, regressor precision 3) and the fp16x3 SMPL modes.
+ *     The fp32 routes use fp32-input MFMA (exact fmaf chains);
  *   - activations inside the encoder are NHWC fp32; the boundary tensor (network input) is NCHW
  *     exactly as the reference passes it (models/regressor.py:43).
  */
@@ -430,6 +432,24 @@ int straps_conv_fwd_x3p(const unsigned short* x3, long long x_plane_stride,
                         const float* shift, const float* residual, int relu, float* y_nhwc,
                         unsigned short* y_planes, long long y_plane_stride, int batch, int h, int w,
                         int cin, int cout, int kh, int kw, int stride, int pad, int tile_cfg, void* stream);
+/* ---- single-product bf16 route (csrc/conv_bf16.hip): eval-mode forward only, no gradients ----
+ * Every fp32 operand is rounded to the nearest-even bf16 and each term is ONE bf16 product, accumulated in fp32: 1/6 of the bf16x3
+ * route's matrix work and 1/3 of its operand bytes, at the accuracy of bf16 operands (relative 2^-9 per operand), not fp32's.
+ * straps_split_bf16_cm: x [rows][c] fp32 (c % 32 == 0) -> rn_bf16(x) as ONE chunk-major plane [rows * c] (the layout of plane 0 of
+ *   straps_split3_bf16_cm).
+ * straps_pack_conv_weight_bf16: OIHW fp32 weights -> rn_bf16 as one chunk-major plane of the forward layout (the layout of plane 0 of
+ *   straps_pack_conv_weights_batched_x3's krsc_planes for a single layer at first = 0); cin % 32 == 0.
+ * straps_conv_fwd_bf16: y = act(conv(x1, w1) * scale + shift + residual) on one bf16 plane per operand (cin % 64 == 0, cout % 64 == 0);
+ *   writes y (fp32 NHWC, may be NULL) and/or y_plane (rn_bf16(y) as one chunk-major plane, may be NULL; not both NULL) -- the next
+ *   convolution's operand.  scale / shift / residual may be NULL.  tile_cfg: 0 = automatic; 1..10 force a tile configuration (tools
+ *   and tests; a configuration the geometry does not admit is refused, never replaced).
+ * straps_conv_bf16_tile_choice: the configuration tile_cfg = 0 takes for this geometry (1..10), -1 if not covered.               */
+int straps_split_bf16_cm(const float* x, unsigned short* plane, long long rows, int c, void* stream);
+int straps_pack_conv_weight_bf16(const float* w_oihw, unsigned short* w_plane, int cout, int cin, int kh, int kw, void* stream);
+int straps_conv_bf16_tile_choice(int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad);
+int straps_conv_fwd_bf16(const unsigned short* x1, const unsigned short* w1_krsc, const float* scale, const float* shift,
+                         const float* residual, int relu, float* y_nhwc, unsigned short* y_plane, int batch, int h, int w,
+                         int cin, int cout, int kh, int kw, int stride, int pad, int tile_cfg, void* stream);
 int straps_conv_dgrad_x3(const unsigned short* dy3, long long dy_plane_stride,
                          const unsigned short* w3_crsk, long long w_plane_stride,
                          const float* addend, float* dx_nhwc, int batch, int h, int w, int cin,
@@ -746,7 +766,9 @@ int straps_adam_step(float* params, const float* grads, float* exp_avg, float* e
  * statistics, then the IEF iterations.  Inference only (no gradients).  The launches are those SingleInputRegressor.eval() makes, with
  * the same arguments (same convolution routes, tile_cfg 0), so the results are bit-identical to the module's.
  *
- * desc: layers 18 | 50; in_channels 1..256; ief_iters 1..64; precision 0 = bf16x3 (ResNet's default conv_precision) | 1 = fp32.
+ * desc: layers 18 | 50; in_channels 1..256; ief_iters 1..64; precision 0 = bf16x3 (ResNet's default conv_precision) | 1 = fp32 |
+ *   3 = bf16 (single-product bf16 convolutions, straps_conv_fwd_bf16: inference only -- every train-mode entry point below rejects it;
+ *   its prepared buffer holds one weight plane, smaller than precision 0's three).  2 is unassigned and invalid.
  *
  * params: ONE flat fp32 device buffer of straps_regressor_param_floats() floats: every tensor of the regressor's state_dict(), in
  *   its order, flattened row-major, WITHOUT the `num_batches_tracked` entries and WITHOUT the `ief_module.ief_layers.*` aliases of
@@ -772,7 +794,7 @@ typedef struct {
     int layers;        /* 18 | 50 */
     int in_channels;   /* >= 1 (reference: 1 or 18) */
     int ief_iters;     /* >= 1 (reference: 3) */
-    int precision;     /* 0 = bf16x3, 1 = fp32 */
+    int precision;     /* 0 = bf16x3, 1 = fp32, 3 = bf16 (inference only); 2 is unassigned */
 } straps_regressor_desc_t;
 size_t straps_regressor_param_floats(const straps_regressor_desc_t* desc);
 size_t straps_regressor_prepared_bytes(const straps_regressor_desc_t* desc);

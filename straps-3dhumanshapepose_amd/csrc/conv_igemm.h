@@ -92,7 +92,8 @@ __device__ __forceinline__ void epi_lds_barrier() {
 // row): BN scale/shift, residual/addend, ReLU fused; returns the per-lane (sum, sum of squares) of the raw values for the
 // training-mode batch statistics.
 // (BNR: also accumulate the BatchNorm-backward sums described at ConvP::bnr_raw into d1 / d2 -- register arrays of the caller)
-template <int BM, int BN, int WGM, int WGN, bool BNR>
+// NYPL: bf16 planes of the eval-mode plane output (p.yplanes): 3 = the bf16x3 route's exact triple, 1 = the single-plane bf16 route's rn_bf16(v)
+template <int BM, int BN, int WGM, int WGN, bool BNR, int NYPL = 3>
 __device__ __forceinline__ void igemm_store_rows_impl(const ConvP& p, const ConvP::Class& c, const f32x16 (&acc)[BM / WGM / 32][BN / WGN / 32], int m0,
                                                       int n0, float (&s1)[BN / WGN / 32], float (&s2)[BN / WGN / 32], double (&d1)[BN / WGN / 32],
                                                       double (&d2)[BN / WGN / 32]) {
@@ -216,12 +217,16 @@ __device__ __forceinline__ void igemm_store_rows_impl(const ConvP& p, const Conv
                             if (!BNR || p.y) p.y[o] = v;
                             if constexpr (BNR) {
                                 if (p.yplanes) {
+                                    if constexpr (NYPL == 1) {
+                                        p.yplanes[cm_index(pixr[r], n0 + wn * WTN + j * 32 + (lane & 31), p.yrows)] = bf16_rn(v);
+                                    } else {
                                     u16 b1, b2, b3;
                                     split3(v, b1, b2, b3);
                                     const long long oc = cm_index(pixr[r], n0 + wn * WTN + j * 32 + (lane & 31), p.yrows);
                                     p.yplanes[oc] = b1;
                                     p.yplanes[p.yps + oc] = b2;
                                     p.yplanes[2 * p.yps + oc] = b3;
+                                    }
                                 }
                                 if (bnr) {
                                     const bool on = p.bnr_bits ? (((__float_as_uint(yo[q][j]) >> (lane & 31)) & 1u) != 0)
@@ -806,6 +811,19 @@ template <int BM, int BN, int WGM, int WGN>
 struct X3Epilogue<BM, BN, WGM, WGN, 0> : IgemmEpilogue<BM, BN, WGM, WGN> {};
 template <int BM, int BN, int WGM, int WGN>
 struct X3Epilogue<BM, BN, WGM, WGN, 2> : LeanDgradEpilogue<BM, BN, WGM, WGN, false> {};
+// EPI = 3: the single-plane bf16 route's eval forward (conv_bf16.hip) -- the shared epilogue with ONE bf16 plane of the result (rn_bf16) in place of three
+template <int BM, int BN, int WGM, int WGN>
+struct X3Epilogue<BM, BN, WGM, WGN, 3> : IgemmEpilogue<BM, BN, WGM, WGN> {
+    template <bool PRE = true>
+    __device__ __forceinline__ void finish(const ConvP& p, const ConvP::Class& c, const f32x16 (&acc)[BM / WGM / 32][BN / WGN / 32], float (&s1)[BN / WGN / 32],
+                                           float (&s2)[BN / WGN / 32], double (&d1)[BN / WGN / 32], double (&d2)[BN / WGN / 32]) {
+        if (!this->look) {
+            igemm_store_rows_impl<BM, BN, WGM, WGN, true, 1>(p, c, acc, this->m0, this->n0, s1, s2, d1, d2);
+            return;
+        }
+        this->template run<PRE>(acc, s1, s2, d1, d2);
+    }
+};
 
 template <int BM, int BN, int WGM = 2, int WGN = 2>
 __device__ __forceinline__ void igemm_store_rows(const ConvP& p, const ConvP::Class& c, const f32x16 (&acc)[BM / WGM / 32][BN / WGN / 32], int m0, int n0,

@@ -2,6 +2,9 @@
 // templates, in a header since round 6: conv_x3.hip instantiates them with the shared epilogue of conv_igemm.h (EPI = 0: every fused form),
 // conv_x3_lean.hip with the lean epilogues (EPI = 1: raw result + statistics, a training step's forward; EPI = 2: a data gradient with addend / ReLU
 // bits / fused BatchNorm sums) -- two translation units, compiled in parallel.  See conv_x3.hip for the arithmetic and the layouts.
+// PL (last template parameter; 0 = the bf16x3 kernels, unchanged): the single-plane bf16 route of conv_bf16.hip -- ONE bf16 plane per operand, one product
+// per term, and PL consecutive 32-channel K chunks per stage in the three plane slots' place (the launcher sets the plane strides to the chunk strides:
+// slot s of a stage is chunk q * PL + s), so that a barrier and a copy wait cover PL chunks of matrix work instead of one.
 #pragma once
 #include "conv_igemm.h"
 
@@ -24,7 +27,7 @@ __device__ __forceinline__ int swz3(int r) { return (r >> 3) & 3; }
 //   publishes chunk q+1 sits BETWEEN the two MFMA blocks of chunk q: k step 1 of chunk q is read before it, k step 0 of chunk q+1
 //   right after it, each half a chunk ahead of its MFMAs (no LDS latency in front of an MFMA block), and the stage of chunk q --
 //   dead once every wave is past that barrier -- is refilled with chunk q+NST during the second block (copies run NST chunks ahead).
-template <int BM, int BN, int WGM, int WGN, int NST, int ABL = 0, bool PIPE = false, int EPI = 0>
+template <int BM, int BN, int WGM, int WGN, int NST, int ABL = 0, bool PIPE = false, int EPI = 0, int PL = 0>
 __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) {
     const ConvP::Class& c = p.cls[blockIdx.y];
     const int cMh = c.Mh, cMw = c.Mw, cM = c.M, cMT = c.MT, cntaps = c.ntaps;
@@ -35,12 +38,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) 
     constexpr int WTM = BM / WGM, WTN = BN / WGN, MI = WTM / 32, NI = WTN / 32;
     constexpr int AP = BM / RPP, BP = BN / RPP;                // copy passes
     static_assert(BM % RPP == 0 && BN % RPP == 0 && WTM % 32 == 0 && WTN % 32 == 0, "tile / wave grid mismatch");
-    constexpr int NPIECE = 3 * (AP + BP);                      // LDS-DMA instructions per thread and chunk
-    constexpr int NMFMA = 2 * 6 * MI * NI;
+    constexpr int NSB = PL ? PL : 3;                           // operand slots per stage: three planes, or PL K chunks of one plane
+    constexpr int NPROD = PL ? PL : 6;                         // products per (fragment pair, 16-wide k step)
+    constexpr int KD = PL ? PL : 1;                            // 32-channel chunks per stage
+    constexpr int NPIECE = NSB * (AP + BP);                    // LDS-DMA instructions per thread and chunk
+    constexpr int NMFMA = 2 * NPROD * MI * NI;
     constexpr int GAP = NMFMA / NPIECE > 0 ? NMFMA / NPIECE : 1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    u16* As = reinterpret_cast<u16*>(smem);       // [NST stages][3 planes][BM][32]
-    u16* Bs = As + NST * 3 * BM * 32;             // [NST stages][3 planes][BN][32]
+    u16* As = reinterpret_cast<u16*>(smem);       // [NST stages][NSB planes][BM][32]
+    u16* Bs = As + NST * NSB * BM * 32;           // [NST stages][NSB planes][BN][32]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WGN, wn = wave % WGN;
@@ -76,10 +82,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) 
 #pragma unroll
     for (int q = 0; q < BP; ++q) wrow[q] = wg + (n0 + lr + RPP * q) * 32 + lc * 8;      // + ((tap * cchunks + chunk) * Cout) * 32
 
-    const int cchunks = p.Cin >> 5;
+    const int cchunks = (p.Cin >> 5) / KD;
     const int nchunks = cntaps * cchunks;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int a_cstep = p.xrows * 32, b_cstep = p.Cout * 32;      // one channel chunk on: elements
+    const int a_cstep = p.xrows * 32 * KD, b_cstep = p.Cout * 32 * KD;      // one channel chunk (stage) on: elements
 
     const u16* a_src[AP];
     long long a_ps[AP];            // plane stride, 0 for a padding pixel (all three planes read the zero constant)
@@ -110,10 +116,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) 
         const int plane = idx / (AP + BP), r = idx % (AP + BP);
         if (r < AP) {
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[r] + plane * a_ps[r]),
-                                             (__attribute__((address_space(3))) void*)(As + ((stage * 3 + plane) * BM + RPP * r + 16 * wave_u) * 32), 16, 0, 0);
+                                             (__attribute__((address_space(3))) void*)(As + ((stage * NSB + plane) * BM + RPP * r + 16 * wave_u) * 32), 16, 0, 0);
         } else {
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[r - AP] + plane * p.wps),
-                                             (__attribute__((address_space(3))) void*)(Bs + ((stage * 3 + plane) * BN + RPP * (r - AP) + 16 * wave_u) * 32), 16, 0, 0);
+                                             (__attribute__((address_space(3))) void*)(Bs + ((stage * NSB + plane) * BN + RPP * (r - AP) + 16 * wave_u) * 32), 16, 0, 0);
         }
     };
     auto advance = [&]() {
@@ -163,15 +169,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) 
         asm volatile("" ::: "memory");
         // the last chunk: no copy wait follows -- the epilogue's first operands are fetched under this chunk's matrix work (conv_igemm.h)
         if constexpr (decltype(last_c)::value) ep.prefetch();
-        const u16* Ab = As + (stage * 3 * BM + wm * WTM) * 32;
-        const u16* Bb = Bs + (stage * 3 * BN + wn * WTN) * 32;
+        const u16* Ab = As + (stage * NSB * BM + wm * WTM) * 32;
+        const u16* Bb = Bs + (stage * NSB * BN + wn * WTN) * 32;
         int cnt = 0;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 a[MI][3], b[NI][3];
+            bf16x8 a[MI][NSB], b[NI][NSB];
             if constexpr (ABL == 3) {      // no fragment reads either: the matrix work on whatever the registers hold
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
+                for (int pl = 0; pl < NSB; ++pl) {
 #pragma unroll
                     for (int i = 0; i < MI; ++i) asm volatile("" : "=v"(a[i][pl]));
 #pragma unroll
@@ -179,19 +185,19 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) 
                 }
             }
 #pragma unroll
-            for (int pl = 0; pl < 3 && ABL != 3; ++pl) {
+            for (int pl = 0; pl < NSB && ABL != 3; ++pl) {
 #pragma unroll
                 for (int i = 0; i < MI; ++i) a[i][pl] = *reinterpret_cast<const bf16x8*>(Ab + (pl * BM + i * 32) * 32 + fo[kk]);
 #pragma unroll
                 for (int j = 0; j < NI; ++j) b[j][pl] = *reinterpret_cast<const bf16x8*>(Bb + (pl * BN + j * 32) * 32 + fo[kk]);
             }
 #pragma unroll
-            for (int t = 0; t < 6; ++t)
+            for (int t = 0; t < NPROD; ++t)
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
                     for (int j = 0; j < NI; ++j) {
-                        if constexpr (ABL != 1) acc[i][j] = mfma_bf16(a[i][TA[t]], b[j][TB[t]], acc[i][j]);
+                        if constexpr (ABL != 1) acc[i][j] = mfma_bf16(a[i][PL ? t : TA[t]], b[j][PL ? t : TB[t]], acc[i][j]);
                         if (MORE && cnt % GAP == GAP - 1 && cnt / GAP < NPIECE) piece(nstage, cnt / GAP);
                         ++cnt;
                     }
@@ -203,12 +209,12 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) 
         }
     };
     if constexpr (PIPE) {
-        bf16x8 fa[2][MI][3], fb[2][NI][3];
+        bf16x8 fa[2][MI][NSB], fb[2][NI][NSB];
         auto load_frags = [&](int stage, int kk, int set) {
-            const u16* Ab = As + (stage * 3 * BM + wm * WTM) * 32;
-            const u16* Bb = Bs + (stage * 3 * BN + wn * WTN) * 32;
+            const u16* Ab = As + (stage * NSB * BM + wm * WTM) * 32;
+            const u16* Bb = Bs + (stage * NSB * BN + wn * WTN) * 32;
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
+            for (int pl = 0; pl < NSB; ++pl) {
 #pragma unroll
                 for (int i = 0; i < MI; ++i) fa[set][i][pl] = *reinterpret_cast<const bf16x8*>(Ab + (pl * BM + i * 32) * 32 + fo[kk]);
 #pragma unroll
@@ -220,12 +226,12 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) 
             constexpr bool more = decltype(more_c)::value;      // (compile-time: a run-time test per copy splits the block at every MFMA)
             int cnt = 0;
 #pragma unroll
-            for (int t = 0; t < 6; ++t)
+            for (int t = 0; t < NPROD; ++t)
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
                     for (int j = 0; j < NI; ++j) {
-                        acc[i][j] = mfma_bf16(fa[set][i][TA[t]], fb[set][j][TB[t]], acc[i][j]);
+                        acc[i][j] = mfma_bf16(fa[set][i][PL ? t : TA[t]], fb[set][j][PL ? t : TB[t]], acc[i][j]);
                         if (set == 1 && cnt % GAP2 == GAP2 - 1 && cnt / GAP2 < NPIECE) { if (more) piece(nstage, cnt / GAP2); }
                         ++cnt;
                     }
@@ -315,7 +321,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3_kernel(ConvP p) 
 // copy; wait; barrier) instead of a chunk ahead: the co-resident workgroup computes meanwhile.  123 us against 137 us for the im2col tile
 // on the layer1 shape (tools/x3d_probe.py): the 64-channel layers are bound by the L2 -> CU operand stream, and this form fetches every
 // input pixel once per channel chunk instead of once per tap without giving up the second workgroup.
-template <int BM, int BN, int WGM, int WGN, int NST, int PS, int PBUF = 2, int EPI = 0>
+template <int BM, int BN, int WGM, int WGN, int NST, int PS, int PBUF = 2, int EPI = 0, int PL = 0>
 __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p) {
     const ConvP::Class& c = p.cls[0];
     const int cntaps = c.ntaps;
@@ -325,14 +331,17 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p)
     constexpr int WTM = BM / WGM, WTN = BN / WGN, MI = WTM / 32, NI = WTN / 32;
     constexpr int BP = BN / RPP;
     static_assert(BN % RPP == 0 && WTM % 32 == 0 && WTN % 32 == 0 && PS % 16 == 0, "tile / wave grid mismatch");
-    constexpr int NPB = 3 * BP;                                // weight copies per thread and step
+    constexpr int NSB = PL ? PL : 3;                           // operand slots per stage / patch: three planes, or PL K chunks of one plane
+    constexpr int NPROD = PL ? PL : 6;                         // products per (fragment pair, 16-wide k step)
+    constexpr int KD = PL ? PL : 1;                            // 32-channel chunks per step
+    constexpr int NPB = NSB * BP;                              // weight copies per thread and step
     constexpr int NPA = (PS * 4 + NTH - 1) / NTH;              // patch copy rounds per plane (the last one may cover only some waves)
-    constexpr int NMFMA = 2 * 6 * MI * NI;
+    constexpr int NMFMA = 2 * NPROD * MI * NI;
     constexpr int GAP = NMFMA / NPB > 0 ? NMFMA / NPB : 1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     static_assert(PBUF == 1 || PBUF == 2, "one or two patch buffers");
-    u16* As = reinterpret_cast<u16*>(smem);       // [PBUF patch buffers][3 planes][PS slots][32]
-    u16* Bs = As + PBUF * 3 * PS * 32;            // [NST stages][3 planes][BN][32]
+    u16* As = reinterpret_cast<u16*>(smem);       // [PBUF patch buffers][NSB planes][PS slots][32]
+    u16* Bs = As + PBUF * NSB * PS * 32;          // [NST stages][NSB planes][BN][32]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WGN, wn = wave % WGN;
@@ -367,16 +376,16 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p)
     const u16* zsrc = reinterpret_cast<const u16*>(k_zero16_x3);
     asm volatile("" : "+s"(zsrc));
     auto patch_dma = [&](int cc) {
-        u16* dst = As + (PBUF == 2 ? (cc & 1) : 0) * (3 * PS * 32);
+        u16* dst = As + (PBUF == 2 ? (cc & 1) : 0) * (NSB * PS * 32);
 #pragma unroll
         for (int pi = 0; pi < NPA; ++pi) {
             if (pi * (NTH / 4) + 16 * wave_u >= nslots) break;                 // wave-uniform: nothing of this round lies inside the patch
             if (pi * (NTH / 4) + 16 * wave_u >= PS) break;
             const bool ok = poff[pi] >= 0;
-            const u16* src = ok ? xg + (poff[pi] + (long long)cc * p.xrows * 32) : zsrc;
+            const u16* src = ok ? xg + (poff[pi] + (long long)(cc * KD) * p.xrows * 32) : zsrc;
             const long long ps = ok ? p.xps : 0;
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
+            for (int pl = 0; pl < NSB; ++pl)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + pl * ps),
                                                  (__attribute__((address_space(3))) void*)(dst + (pl * PS + pi * (NTH / 4) + 16 * wave_u) * 32), 16, 0, 0);
         }
@@ -388,7 +397,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p)
     const u16* wrow[BP];
 #pragma unroll
     for (int q = 0; q < BP; ++q) wrow[q] = wg + (n0 + lr + RPP * q) * 32 + lc * 8;      // + ((tap * cchunks + chunk) * Cout) * 32
-    const int cchunks = p.Cin >> 5;
+    const int cchunks = (p.Cin >> 5) / KD;
     const int nsteps = cntaps * cchunks;
     const int tl = lane < 9 ? lane : 0;
     const int v_tw = c.tap_w[tl];
@@ -397,8 +406,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p)
     auto piece = [&](int stage, int idx) {
         const int plane = idx / BP, r = idx % BP;
         const int tw = __builtin_amdgcn_readlane(v_tw, i_tap);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow[r] + (long long)(tw * cchunks + i_cc) * p.Cout * 32 + plane * p.wps),
-                                         (__attribute__((address_space(3))) void*)(Bs + ((stage * 3 + plane) * BN + RPP * r + 16 * wave_u) * 32), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow[r] + (long long)((tw * cchunks + i_cc) * KD) * p.Cout * 32 + plane * p.wps),
+                                         (__attribute__((address_space(3))) void*)(Bs + ((stage * NSB + plane) * BN + RPP * r + 16 * wave_u) * 32), 16, 0, 0);
     };
     auto advance = [&]() {
         if (++i_tap == cntaps) { i_tap = 0; ++i_cc; }
@@ -459,8 +468,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p)
         }
         // the last step: no copy wait follows -- the epilogue's first operands are fetched under this step's matrix work (conv_igemm.h)
         if constexpr (decltype(last_c)::value) ep.prefetch();
-        const u16* Ap = As + (PBUF == 2 ? (c_cc & 1) : 0) * (3 * PS * 32);
-        const u16* Bb = Bs + (stage * 3 * BN + wn * WTN) * 32;
+        const u16* Ap = As + (PBUF == 2 ? (c_cc & 1) : 0) * (NSB * PS * 32);
+        const u16* Bb = Bs + (stage * NSB * BN + wn * WTN) * 32;
         const int tsh = __builtin_amdgcn_readlane(v_sh, c_tap);
         int ao[MI][2];
 #pragma unroll
@@ -472,21 +481,21 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p)
         int cnt = 0;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 a[MI][3], b[NI][3];
+            bf16x8 a[MI][NSB], b[NI][NSB];
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
+            for (int pl = 0; pl < NSB; ++pl) {
 #pragma unroll
                 for (int i = 0; i < MI; ++i) a[i][pl] = *reinterpret_cast<const bf16x8*>(Ap + pl * PS * 32 + ao[i][kk]);
 #pragma unroll
                 for (int j = 0; j < NI; ++j) b[j][pl] = *reinterpret_cast<const bf16x8*>(Bb + (pl * BN + j * 32) * 32 + fo[kk]);
             }
 #pragma unroll
-            for (int t = 0; t < 6; ++t)
+            for (int t = 0; t < NPROD; ++t)
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
                     for (int j = 0; j < NI; ++j) {
-                        acc[i][j] = mfma_bf16(a[i][TA[t]], b[j][TB[t]], acc[i][j]);
+                        acc[i][j] = mfma_bf16(a[i][PL ? t : TA[t]], b[j][PL ? t : TB[t]], acc[i][j]);
                         if (MORE && cnt % GAP == GAP - 1 && cnt / GAP < NPB) piece(nstage, cnt / GAP);
                         ++cnt;
                     }
@@ -526,15 +535,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p)
     clk_end(p, clk);
 }
 
-template <int BM, int BN, int WGM, int WGN, int NST, int PS, int PBUF = 2, int EPI = 0>
+template <int BM, int BN, int WGM, int WGN, int NST, int PS, int PBUF = 2, int EPI = 0, int PL = 0>
 int launch_x3h(const ConvP& p0, hipStream_t st) {
     ConvP p = p0;
     p.NT = p.Cout / BN;
     p.cls[0].MT = p.cls[0].M / BM;
     p.bnr_base[0] = 0;
-    const size_t lds = ((size_t)PBUF * 3 * PS + (size_t)NST * 3 * BN) * 32 * sizeof(u16);
-    STRAPS_RAISE_LDS((conv_igemm_x3h_kernel<BM, BN, WGM, WGN, NST, PS, PBUF, EPI>), lds, "conv_igemm_x3h_kernel");
-    hipLaunchKernelGGL((conv_igemm_x3h_kernel<BM, BN, WGM, WGN, NST, PS, PBUF, EPI>), dim3(p.cls[0].MT * p.NT, 1), dim3(64 * WGM * WGN), lds, st, p);
+    const size_t lds = ((size_t)PBUF * (PL ? PL : 3) * PS + (size_t)NST * (PL ? PL : 3) * BN) * 32 * sizeof(u16);
+    STRAPS_RAISE_LDS((conv_igemm_x3h_kernel<BM, BN, WGM, WGN, NST, PS, PBUF, EPI, PL>), lds, "conv_igemm_x3h_kernel");
+    hipLaunchKernelGGL((conv_igemm_x3h_kernel<BM, BN, WGM, WGN, NST, PS, PBUF, EPI, PL>), dim3(p.cls[0].MT * p.NT, 1), dim3(64 * WGM * WGN), lds, st, p);
     STRAPS_CHECK_LAUNCH("conv_igemm_x3h_kernel");
     return STRAPS_OK;
 }
@@ -554,7 +563,7 @@ inline int halo_patch_slots(const ConvP& p) {
     return (BM / p.W + 2) * (p.W + 2);
 }
 
-template <int BM, int BN, int WGM, int WGN, int NST, int ABL = 0, bool PIPE = false, int EPI = 0>
+template <int BM, int BN, int WGM, int WGN, int NST, int ABL = 0, bool PIPE = false, int EPI = 0, int PL = 0>
 int launch_x3(const ConvP& p0, hipStream_t st) {
     ConvP p = p0;
     p.NT = p.Cout / BN;
@@ -566,9 +575,9 @@ int launch_x3(const ConvP& p0, hipStream_t st) {
         p.bnr_base[i] = base;                   // (BatchNorm-backward partials: one block per M tile, classes one after the other)
         base += p.cls[i].MT;
     }
-    const size_t lds = (size_t)NST * 3 * (BM + BN) * 32 * sizeof(u16);
-    STRAPS_RAISE_LDS((conv_igemm_x3_kernel<BM, BN, WGM, WGN, NST, ABL, PIPE, EPI>), lds, "conv_igemm_x3_kernel");
-    hipLaunchKernelGGL((conv_igemm_x3_kernel<BM, BN, WGM, WGN, NST, ABL, PIPE, EPI>), dim3(maxblk, p.ncls), dim3(64 * WGM * WGN), lds, st, p);
+    const size_t lds = (size_t)NST * (PL ? PL : 3) * (BM + BN) * 32 * sizeof(u16);
+    STRAPS_RAISE_LDS((conv_igemm_x3_kernel<BM, BN, WGM, WGN, NST, ABL, PIPE, EPI, PL>), lds, "conv_igemm_x3_kernel");
+    hipLaunchKernelGGL((conv_igemm_x3_kernel<BM, BN, WGM, WGN, NST, ABL, PIPE, EPI, PL>), dim3(maxblk, p.ncls), dim3(64 * WGM * WGN), lds, st, p);
     STRAPS_CHECK_LAUNCH("conv_igemm_x3_kernel");
     return STRAPS_OK;
 }

@@ -46,7 +46,7 @@ struct Plan {
     long long fc1w_off, fc1b_off, fc2w_off, fc2b_off, fc3w_off, fc3b_off, init_off, param_floats;
     // prepared buffer (bytes)
     size_t stem_w, stem_ss, table, planes, w1f, w1e, w3, fc1b, fc2w, fc2b, fc3b, init, prepared_bytes;
-    long long ps;                   // plane stride of the bf16x3 weight planes
+    long long ps;                   // plane stride of the bf16x3 weight planes (bf16: the element count of the one plane, rounded up to 8)
 };
 
 // nullptr + text when the description is invalid (the text names the field)
@@ -56,7 +56,8 @@ const char* check_desc(const straps_regressor_desc_t* d) {
     // (the stem keeps all input channels' weights in LDS: 256 channels fit its 160 KiB)
     if (d->in_channels < 1 || d->in_channels > 256) return "`in_channels` must be in [1, 256]";
     if (d->ief_iters < 1 || d->ief_iters > 64) return "`ief_iters` must be in [1, 64]";
-    if (d->precision != 0 && d->precision != 1) return "`precision` must be 0 (bf16x3) or 1 (fp32)";
+    // (2 is unassigned: it stays invalid)
+    if (d->precision != 0 && d->precision != 1 && d->precision != 3) return "`precision` must be 0 (bf16x3), 1 (fp32) or 3 (bf16)";
     return nullptr;
 }
 
@@ -129,6 +130,8 @@ void make_plan(const straps_regressor_desc_t* d, Plan& p) {
     if (p.precision == 0) {
         p.table = take((size_t)p.nconvs * sizeof(straps_pack_desc_t));
         p.planes = take(3 * (size_t)p.ps * sizeof(unsigned short));
+    } else if (p.precision == 3) {      // bf16: one plane, every layer at its `first` (multiples of 64 x 64 elements: 16-byte aligned)
+        p.planes = take((size_t)p.ps * sizeof(unsigned short));
     } else {
         for (int i = 0; i < p.nconvs; ++i) {
             Conv& cv = *p.convs[i];
@@ -148,9 +151,9 @@ void make_plan(const straps_regressor_desc_t* d, Plan& p) {
 
 // Workspace slots for one (B, H, W).  Between the stem and the pooled input only the stem output lives; afterwards a fixed set of
 // slots is reused by every residual unit:
-//   io[0], io[1] : unit inputs / outputs (ping-pong), fp32 + (bf16x3) their planes -- io[0] first holds the pooled stem output
+//   io[0], io[1] : unit inputs / outputs (ping-pong), fp32 + (bf16x3) their planes / (bf16) their plane -- io[0] first holds the pooled stem output
 //   idt          : fp32 output of a unit's projection (the identity of units with a downsample)
-//   mid[0..1]    : outputs of a unit's inner convolutions (bf16x3: planes only, nothing reads their fp32 form; fp32: fp32)
+//   mid[0..1]    : outputs of a unit's inner convolutions (bf16x3 / bf16: planes only, nothing reads their fp32 form; fp32: fp32)
 //   ief          : features, fc1 feature half, the iterations' estimates [T + 1][B][160], one hidden pair [B][H1], [B][H2]
 // The stem output overlaps everything behind io[0]: it is dead once the max pool has written io[0].
 struct Work {
@@ -162,7 +165,7 @@ struct Work {
 
 bool make_work(const Plan& p, int B, int H, int W, Work& w) {
     if (B <= 0 || H < 7 || W < 7) return false;
-    const bool x3 = p.precision == 0;
+    const int npl = p.precision == 0 ? 3 : p.precision == 3 ? 1 : 0;      // activation planes
     w.Hs = conv_out(H, 7, 2, 3); w.Ws = conv_out(W, 7, 2, 3);
     w.Hp = conv_out(w.Hs, 3, 2, 1); w.Wp = conv_out(w.Ws, 3, 2, 1);
     long long io = (long long)B * w.Hp * w.Wp * 64, idt = 0, mid[2] = {0, 0};
@@ -191,14 +194,14 @@ bool make_work(const Plan& p, int B, int H, int W, Work& w) {
     auto take = [&](size_t bytes) { const size_t o = b; b = align_up(b + bytes); return o; };
     w.nzmask = take(straps_stem_nzmask_words(B, p.cin, H, W) * sizeof(uint32_t));
     w.io[0] = take(io * sizeof(float));
-    w.io_planes[0] = x3 ? take(3 * (size_t)w.io_ps * sizeof(unsigned short)) : 0;
+    w.io_planes[0] = npl ? take(npl * (size_t)w.io_ps * sizeof(unsigned short)) : 0;
     const size_t tail = b;
     w.io[1] = take(io * sizeof(float));
-    w.io_planes[1] = x3 ? take(3 * (size_t)w.io_ps * sizeof(unsigned short)) : 0;
+    w.io_planes[1] = npl ? take(npl * (size_t)w.io_ps * sizeof(unsigned short)) : 0;
     w.idt = take((idt ? idt : 1) * sizeof(float));
     for (int i = 0; i < 2; ++i) {
         const size_t n = mid[i] ? (size_t)mid[i] : 1;
-        w.mid[i] = x3 ? take(3 * (size_t)round8(n) * sizeof(unsigned short)) : take(n * sizeof(float));
+        w.mid[i] = npl ? take(npl * (size_t)round8(n) * sizeof(unsigned short)) : take(n * sizeof(float));
     }
     w.feat = take((size_t)B * p.F * sizeof(float));
     w.c1 = take((size_t)B * p.H1 * sizeof(float));
@@ -287,6 +290,12 @@ extern "C" int straps_regressor_prepare(const straps_regressor_desc_t* d, const 
                                                     (unsigned short*)(pb + p.planes), nullptr, p.ps, stream));
         // (the descriptor table lives in this frame: it must have reached the device before the function returns)
         RG_HIP(hipStreamSynchronize(st), "hipStreamSynchronize");
+    } else if (p.precision == 3) {
+        // bf16: every layer's forward weights as one rn_bf16 plane (ResNet._packed_weight_bf16)
+        for (int i = 0; i < p.nconvs; ++i) {
+            const Conv& cv = *p.convs[i];
+            RG_CALL(straps_pack_conv_weight_bf16(params + cv.w_off, (unsigned short*)(pb + p.planes) + cv.first, cv.cout, cv.cin, cv.k, cv.k, stream));
+        }
     } else {
         for (int i = 0; i < p.nconvs; ++i) {
             const Conv& cv = *p.convs[i];
@@ -325,7 +334,7 @@ extern "C" int straps_regressor_fwd_infer(const straps_regressor_desc_t* d, cons
     STRAPS_REQUIRE(make_work(p, batch, h, w, wk), "straps_regressor_fwd_infer: input %d x %d is too small for resnet%d", h, w, p.layers);
     STRAPS_REQUIRE(workspace_bytes >= wk.bytes, "straps_regressor_fwd_infer: `workspace_bytes` is %zu, this batch needs %zu (straps_regressor_workspace_bytes)",
                    workspace_bytes, wk.bytes);
-    const bool x3 = p.precision == 0;
+    const bool x3 = p.precision == 0, b16 = p.precision == 3;
     const char* pb = (const char*)prepared;
     char* ws = (char*)workspace;
     auto pf = [&](size_t off) { return (const float*)(pb + off); };
@@ -342,12 +351,14 @@ extern "C" int straps_regressor_fwd_infer(const straps_regressor_desc_t* d, cons
     int H = wk.Hp, W = wk.Wp, cur = 0;
     if (x3)      // the pooled input is the only activation split into planes by a pass of its own
         RG_CALL(straps_split3_bf16_cm(wf(wk.io[0]), wp(wk.io_planes[0]), (long long)B * H * W, 64, wk.io_ps, stream));
+    if (b16)
+        RG_CALL(straps_split_bf16_cm(wf(wk.io[0]), wp(wk.io_planes[0]), (long long)B * H * W, 64, stream));
 
     // ---- residual stages (encoder_exec._residual_stages, eval without a tape) ----
     for (int ui = 0; ui < p.nunits; ++ui) {
         const Unit& u = p.units[ui];
         const float* in = wf(wk.io[cur]);
-        const unsigned short* in3 = x3 ? wp(wk.io_planes[cur]) : nullptr;
+        const unsigned short* in3 = (x3 || b16) ? wp(wk.io_planes[cur]) : nullptr;
         const float* idt = in;
         if (u.has_ds) {     // projection: no ReLU, fp32 output only
             const Conv& cv = u.ds;
@@ -355,6 +366,9 @@ extern "C" int straps_regressor_fwd_infer(const straps_regressor_desc_t* d, cons
             if (x3)
                 RG_CALL(straps_conv_fwd_x3(in3, wk.io_ps, wplanes + cv.first, p.ps, ss, ss + cv.cout, nullptr, 0, wf(wk.idt), nullptr,
                                            B, H, W, cv.cin, cv.cout, 1, 1, cv.stride, 0, 0, stream));
+            else if (b16)
+                RG_CALL(straps_conv_fwd_bf16(in3, wplanes + cv.first, ss, ss + cv.cout, nullptr, 0, wf(wk.idt), nullptr, B, H, W, cv.cin, cv.cout, 1, 1,
+                                             cv.stride, 0, 0, stream));
             else
                 RG_CALL(straps_conv_fwd(in, pf(cv.wk_off), ss, ss + cv.cout, nullptr, 0, wf(wk.idt), nullptr, B, H, W, cv.cin, cv.cout, 1, 1,
                                         cv.stride, 0, 0, stream));
@@ -369,12 +383,15 @@ extern "C" int straps_regressor_fwd_infer(const straps_regressor_desc_t* d, cons
             const bool last = ci == u.nconv - 1;
             const float* ss = pf(cv.ss_off);
             const float* res = last ? idt : nullptr;
-            float* y = last ? wf(wk.io[cur ^ 1]) : (x3 ? nullptr : wf(wk.mid[ci]));
-            unsigned short* y3 = x3 ? (last ? wp(wk.io_planes[cur ^ 1]) : wp(wk.mid[ci])) : nullptr;
+            float* y = last ? wf(wk.io[cur ^ 1]) : ((x3 || b16) ? nullptr : wf(wk.mid[ci]));
+            unsigned short* y3 = (x3 || b16) ? (last ? wp(wk.io_planes[cur ^ 1]) : wp(wk.mid[ci])) : nullptr;
             const long long y_ps = last ? wk.io_ps : wk.mid_ps[ci];
             if (x3)      // ReLU outputs write their planes in the epilogue; the fp32 tensor only for a unit's output
                 RG_CALL(straps_conv_fwd_x3p(t3, t_ps, wplanes + cv.first, p.ps, ss, ss + cv.cout, res, 1, y, y3, y_ps,
                                             B, th, tw, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0, stream));
+            else if (b16)      // the same with one plane
+                RG_CALL(straps_conv_fwd_bf16(t3, wplanes + cv.first, ss, ss + cv.cout, res, 1, y, y3, B, th, tw, cv.cin, cv.cout, cv.k, cv.k, cv.stride,
+                                             cv.pad, 0, stream));
             else
                 RG_CALL(straps_conv_fwd(t, pf(cv.wk_off), ss, ss + cv.cout, res, 1, y, nullptr, B, th, tw, cv.cin, cv.cout, cv.k, cv.k,
                                         cv.stride, cv.pad, 0, stream));

@@ -90,7 +90,8 @@ const char* check_desc(const straps_regressor_desc_t* d) {
     if (d->layers != 18 && d->layers != 50) return "`layers` must be 18 or 50";
     if (d->in_channels < 1 || d->in_channels > 256) return "`in_channels` must be in [1, 256]";
     if (d->ief_iters < 1 || d->ief_iters > 64) return "`ief_iters` must be in [1, 64]";
-    if (d->precision != 0 && d->precision != 1) return "`precision` must be 0 (bf16x3) or 1 (fp32)";
+    // (3 = bf16 is an inference-only route: straps_regressor_fwd_infer; no train entry point accepts it)
+    if (d->precision != 0 && d->precision != 1) return "`precision` must be 0 (bf16x3) or 1 (fp32) for training (3 = bf16 is inference-only)";
     return nullptr;
 }
 

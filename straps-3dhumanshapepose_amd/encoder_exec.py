@@ -51,6 +51,7 @@ class _Ctx:
         self.tape = tape
         self.defer_nbt = False        # True: the caller bumps every BatchNorm's num_batches_tracked itself (one fused add)
         self.x3 = False               # bf16x3 convolution route (net.conv_precision)
+        self.bf16 = False             # single-product bf16 route (net.conv_precision == 'bf16': eval mode, no tape -- csrc/conv_bf16.hip)
         self.planes = {}              # bf16x3 route: id(tensor) -> (tensor, planes, plane stride) of the activations split so far
         self.net = None
 
@@ -151,10 +152,19 @@ def weight_planes(L, w, dgrad=False):
     return planes, ps
 
 
+def split1(L, t):
+    """fp32 activation [..., C] (NHWC) -> rn_bf16(t) as ONE chunk-major bf16 plane (the bf16 route's operand; plane 0 of split3's layout)"""
+    C = t.shape[-1]
+    plane = torch.empty((t.numel() + 7) // 8 * 8, device=t.device, dtype=torch.int16)
+    hipabi.check(L.straps_split_bf16_cm(hipabi.ptr(t), hipabi.ptr(plane), t.numel() // C, C, hipabi.stream_ptr()), 'straps_split_bf16_cm')
+    return plane
+
+
 def _planes_of(ctx, t):
+    """(planes, plane stride) of an activation on the bf16x3 route; on the bf16 route (ctx.bf16) its single plane, stride 0"""
     hit = ctx.planes.get(id(t))
     if hit is None or hit[0] is not t:
-        hit = (t,) + split3(ctx.L, t)
+        hit = (t, split1(ctx.L, t), 0) if ctx.bf16 else (t,) + split3(ctx.L, t)
         ctx.planes[id(t)] = hit
     return hit[1], hit[2]
 
@@ -173,6 +183,13 @@ def _conv_launch(ctx, net, x, wpk, conv, ss, residual, relu, y, part, geom, tile
         a0, a1 = (hipabi.ptr(a_bn[0]), hipabi.ptr(a_bn[1])) if a_bn is not None else (None, None)
         hipabi.check(L.straps_conv_fwd_x3f(hipabi.ptr(x), a0, a1, int(a_bn is not None), hipabi.ptr(w3), wps, s0, s1, hipabi.ptr(residual), int(relu), hipabi.ptr(y),
                                            hipabi.ptr(part), B, H, W, Cin, Cout, k, k, stride, pad, tile_cfg, hipabi.stream_ptr()), 'straps_conv_fwd_x3f')
+        return
+    if ctx.bf16:
+        # single-product bf16 route (eval, no tape): a convolution without ReLU (a projection) -- fp32 output only, nothing reads its plane
+        x1, _ = _planes_of(ctx, x)
+        hipabi.check(L.straps_conv_fwd_bf16(hipabi.ptr(x1), hipabi.ptr(net._packed_weight_bf16(conv)), s0, s1, hipabi.ptr(residual), int(relu),
+                                            hipabi.ptr(y), None, B, H, W, Cin, Cout, k, k, stride, pad, tile_cfg, hipabi.stream_ptr()),
+                     'straps_conv_fwd_bf16')
         return
     if getattr(net, 'conv_precision', 'fp32') == 'bf16x3':
         x3, xps = _planes_of(ctx, x)
@@ -204,7 +221,7 @@ def conv_bn(ctx, net, x, B, H, W, conv, bn, relu, residual=None, tile_cfg=0, kee
     Cout, Cin, k = conv.weight.shape[0], conv.weight.shape[1], conv.weight.shape[2]
     stride, pad = conv.stride[0], conv.padding[0]
     Ho, Wo = _conv_out(H, k, stride, pad), _conv_out(W, k, stride, pad)
-    wpk = None if ctx.x3 else net._packed_weight(conv)          # (the bf16x3 route reads the weights' planes: _conv_launch)
+    wpk = None if (ctx.x3 or ctx.bf16) else net._packed_weight(conv)          # (the bf16x3 / bf16 routes read the weights' planes: _conv_launch)
     y = ctx.empty(B, Ho, Wo, Cout)
     rec = None
     if ctx.tape is not None:
@@ -226,6 +243,17 @@ def conv_bn(ctx, net, x, B, H, W, conv, bn, relu, residual=None, tile_cfg=0, kee
                                                hipabi.ptr(y if keep_fp32 else None), hipabi.ptr(yp), yps, B, H, W, Cin, Cout, k, k, stride, pad, tile_cfg,
                                                hipabi.stream_ptr()), 'straps_conv_fwd_x3p')
             ctx.planes[id(y)] = (y, yp, yps)
+            return y, Ho, Wo
+        if ctx.bf16 and relu:
+            # single-product bf16 route: the same, with the output's ONE plane (rn_bf16) written by the epilogue
+            x1, _ = _planes_of(ctx, x)
+            if not keep_fp32:
+                y = x.new_empty(0)
+            yp = torch.empty((B * Ho * Wo * Cout + 7) // 8 * 8, device=x.device, dtype=torch.int16)
+            hipabi.check(L.straps_conv_fwd_bf16(hipabi.ptr(x1), hipabi.ptr(net._packed_weight_bf16(conv)), hipabi.ptr(ss[0]), hipabi.ptr(ss[1]),
+                                                hipabi.ptr(residual), int(relu), hipabi.ptr(y if keep_fp32 else None), hipabi.ptr(yp), B, H, W, Cin, Cout,
+                                                k, k, stride, pad, tile_cfg, hipabi.stream_ptr()), 'straps_conv_fwd_bf16')
+            ctx.planes[id(y)] = (y, yp, 0)
             return y, Ho, Wo
         _conv_launch(ctx, net, x, wpk, conv, ss, residual, relu, y, None, (B, H, W, Cin, Cout, k, stride, pad), tile_cfg)
         return y, Ho, Wo
@@ -262,6 +290,10 @@ def encoder_forward(net, x, tape=None, nzmask=None):
     ctx = _Ctx(x.device, net.training, tape)
     ctx.net = net
     ctx.x3 = getattr(net, 'conv_precision', 'fp32') == 'bf16x3'
+    ctx.bf16 = getattr(net, 'conv_precision', 'fp32') == 'bf16'
+    if ctx.bf16 and (net.training or tape is not None):
+        # (every caller checks this before anything runs -- ResNet.require_route; this is the executor's own guard: no gradient may be dropped)
+        raise RuntimeError("conv_precision='bf16' is an inference-only route: no train-mode or taped forward (use torch.no_grad() and .eval())")
     if net.training:
         net._bn_epoch = getattr(net, '_bn_epoch', 0) + 1      # running statistics are about to change: folded-BN cache entries expire
     ctx.defer_nbt = getattr(net, '_nbt_flat', None) is not None
@@ -355,7 +387,7 @@ def _residual_stages(ctx, net, y, B, H, W, tape):
         for ci, (conv, bn) in enumerate(pairs):
             last = ci == len(pairs) - 1
             keep, planes = True, True
-            if ctx.x3 and not ctx.training and tape is None:
+            if (ctx.x3 or ctx.bf16) and not ctx.training and tape is None:
                 keep = last                     # inference: only a unit's output is read as fp32 (identity of the next unit, pooling)
             ho2, wo2 = _conv_out(h, conv.weight.shape[2], conv.stride[0], conv.padding[0]), _conv_out(w, conv.weight.shape[2], conv.stride[0], conv.padding[0])
             defer = False

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
-SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
+SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
            'regressor.hip', 'regressor_train.hip']
 
@@ -175,6 +175,11 @@ SIGNATURES = {
     'straps_conv_fwd_x3': (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'straps_conv_fwd_x3p': (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'straps_conv_dgrad_x3': (_I, [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # single-product bf16 route, eval-mode forward only (csrc/conv_bf16.hip)
+    'straps_split_bf16_cm': (_I, [_P, _P, _L, _I, _P]),
+    'straps_pack_conv_weight_bf16': (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    'straps_conv_bf16_tile_choice': (_I, [_I] * 9),
+    'straps_conv_fwd_bf16': (_I, [_P, _P, _P, _P, _P, _I, _P, _P] + [_I] * 10 + [_P]),
     'straps_conv_x3_stat_blocks': (_I, [_I] * 10),
     'straps_conv_x3f_supported': (_I, [_I] * 6),
     'straps_conv_fwd_x3f': (_I, [_P, _P, _P, _I, _P, _L, _P, _P, _P, _I, _P, _P] + [_I] * 10 + [_P]),

@@ -11,7 +11,7 @@ import torch.nn as nn
 from . import hipabi
 from .ief_module import EST_LD
 
-PRECISIONS = {'bf16x3': 0, 'fp32': 1}
+PRECISIONS = {'bf16x3': 0, 'fp32': 1, 'bf16': 3}      # (2 is unassigned; 'bf16' = single-product bf16 convolutions, inference only)
 N_PARAMS = 3 + 24 * 6 + 10
 
 
@@ -29,7 +29,7 @@ def regressor_desc(regressor, precision=None):
     enc = regressor.image_encoder
     precision = precision or getattr(enc, 'conv_precision', 'fp32')
     if precision not in PRECISIONS:
-        raise ValueError("precision must be 'bf16x3' or 'fp32' (got %r)" % (precision,))
+        raise ValueError("precision must be 'bf16x3', 'fp32' or 'bf16' (got %r)" % (precision,))
     layers = 18 if enc.kind == 'basic' else 50
     return hipabi.RegressorDesc(layers, enc.in_channels, regressor.ief_module.iterations, PRECISIONS[precision])
 

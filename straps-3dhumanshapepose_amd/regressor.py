@@ -24,6 +24,7 @@ class SingleInputRegressor(nn.Module):
 
     @hipabi.on_tensor_device
     def forward(self, input):
+        self.image_encoder.require_route(input, self.parameters())
         if torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self.parameters())):
             from .autograd_ops import regressor_autograd
             return regressor_autograd(self, input)

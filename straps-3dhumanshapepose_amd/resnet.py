@@ -13,6 +13,7 @@ import torch.nn as nn
 from . import hipabi
 
 BN_EPS = 1e-5
+CONV_PRECISIONS = ('fp32', 'bf16x3', 'bf16')
 
 
 def _check_block_args(name, groups, base_width, dilation, norm_layer):
@@ -99,10 +100,12 @@ class ResNet(nn.Module):
         :158); groups / width_per_group / replace_stride_with_dilation / norm_layer other than their defaults raise: no kernel implements them.
         conv_precision (extension, also an attribute that may be set at any time; NOT part of the state dict): arithmetic of the
         3x3 / 1x1 convolutions -- 'bf16x3' (default): fp32 operands as exact bf16 triples on the bf16 matrix pipe, six products per
-        term, fp32 accumulate (the fp32 chain's accuracy class: tests/test_gpu_conv_x3.py), 'fp32': the exact fp32-input MFMA chain."""
+        term, fp32 accumulate (the fp32 chain's accuracy class: tests/test_gpu_conv_x3.py), 'fp32': the exact fp32-input MFMA chain,
+        'bf16': inference only -- operands rounded to bf16, ONE product per term, fp32 accumulate (csrc/conv_bf16.hip: bf16 accuracy, a
+        fraction of the bf16x3 route's time); an eval-mode forward without gradients (torch.no_grad()), anything else raises."""
         super().__init__()
-        if conv_precision not in ('fp32', 'bf16x3'):
-            raise ValueError("conv_precision must be 'fp32' or 'bf16x3'")
+        if conv_precision not in CONV_PRECISIONS:
+            raise ValueError("conv_precision must be 'fp32', 'bf16x3' or 'bf16'")
         if isinstance(block, str):
             block = {'basic': BasicBlock, 'bottleneck': Bottleneck}[block]
         if block not in (BasicBlock, Bottleneck):
@@ -292,8 +295,36 @@ class ResNet(nn.Module):
             return out
         return self._cached(('wsd', id(self.conv1)), [w], make)
 
+    def require_route(self, x, params=None):
+        """the single-product bf16 route is an eval-mode, gradient-free forward: train mode, or a forward that would need a tape (grad mode
+        with the input or any parameter requiring grad -- of this module, or of `params`, the enclosing module's), raises before any launch."""
+        if getattr(self, 'conv_precision', 'fp32') != 'bf16':
+            return
+        if self.training:
+            raise RuntimeError("conv_precision='bf16' is an inference-only route: the encoder is in train mode (call .eval(), or switch "
+                               "conv_precision to 'bf16x3' for training)")
+        ps = self.parameters() if params is None else params
+        if torch.is_grad_enabled() and ((x is not None and x.requires_grad) or any(p.requires_grad for p in ps)):
+            raise RuntimeError("conv_precision='bf16' has no gradients: run the forward under torch.no_grad() (or switch conv_precision to "
+                               "'bf16x3')")
+
+    def _packed_weight_bf16(self, conv):
+        """rn_bf16 forward weights of one convolution as a single chunk-major plane (straps_pack_conv_weight_bf16) -- the bf16 route's
+        operand; cached under its own key, so the bf16x3 planes and this plane never stand in for each other."""
+        w = conv.weight
+        L = hipabi.lib()
+
+        def make():
+            wd = w.detach().contiguous()
+            out = torch.empty(wd.numel(), device=wd.device, dtype=torch.int16)
+            hipabi.check(L.straps_pack_conv_weight_bf16(hipabi.ptr(wd), hipabi.ptr(out), wd.shape[0], wd.shape[1], wd.shape[2], wd.shape[3],
+                                                        hipabi.stream_ptr()), 'straps_pack_conv_weight_bf16')
+            return out
+        return self._cached(('w1', id(conv)), [w], make)
+
     @hipabi.on_tensor_device
     def forward(self, x):
+        self.require_route(x)
         # grad mode with anything to differentiate: the taped forward + encoder_backward (input and parameter gradients)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             from .autograd_ops import encoder_autograd

@@ -42,6 +42,9 @@ class CompositeTrainer:
             if m.eps != 1e-5 or m.momentum != 0.1 or not m.track_running_stats or not m.affine:
                 raise NotImplementedError('CompositeTrainer: BatchNorm must have eps 1e-5, momentum 0.1, running statistics and affine parameters')
         self.precision = precision or getattr(regressor.image_encoder, 'conv_precision', 'fp32')
+        if self.precision == 'bf16':
+            raise RuntimeError("CompositeTrainer: conv_precision / precision 'bf16' is an inference-only route (no gradients): train on 'bf16x3' "
+                               "or 'fp32'")
         self.desc = regressor_desc(regressor, self.precision)
         self.device = regressor.image_encoder.conv1.weight.device
         hipabi.require_gpu_tensor(regressor.image_encoder.conv1.weight, 'regressor parameters (call .to(device))')

@@ -201,6 +201,8 @@ class TrainStep:
         use_graph: after two eager warm-up steps, capture data generation + forward + loss + backward (~250 kernel
         launches) in one hipGraph and replay it each step; the gradient all-reduce and Adam stay eager launches.
         *_augment_params: the dictionaries of run_train.py:133-190 (defaults = the values that script sets)."""
+        if getattr(regressor.image_encoder, 'conv_precision', 'fp32') == 'bf16':
+            raise RuntimeError("TrainStep: conv_precision='bf16' is an inference-only route (no gradients): train on 'bf16x3' or 'fp32'")
         p0 = next(regressor.parameters())
         if not (isinstance(p0, torch.Tensor) and p0.is_cuda):
             raise RuntimeError('TrainStep: regressor parameters must be GPU tensors (call .to(device) first): the STRAPS hot path runs only '
