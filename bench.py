@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|fwd|smpl | --config 1..4] [--batch B] [--layers 18|50]
     python bench.py ... --dump-outputs DIR    (also write the last timed step's outputs as DIR/<name>.npy)
+    python bench.py ... --full                (also measure everything beyond the headline figure: see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch; inputs are generated / resident in HBM:
@@ -14,9 +15,14 @@ A "step" is one pass of the hot path over one batch; inputs are generated / resi
   smpl  (configs[4]): SMPL-only forward, 65 536 bodies of random (theta, beta) per step x 16 steps = the 1 M bodies BASELINE.json
         names; blend contraction in the three-product fp16 split (--smpl-exact: exact-fp32 MFMA kernel, the A/B).
   --config 3 = configs[3]'s per-GPU shape (train, resnet50, 32 bodies per GPU).
-Rank 0 prints ONE JSON line.  `roofline` = the dominant kernel of the workload, its launches timed
-live with HIP events on the launch stream inside the timed region; `cpu_baseline` = the CPU oracle
-on a bounded sample on this host (rank 0, N = 1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line: `value` / `ms_per_step` of the timed steps, `sclk_mhz` from the clock probe the timed
+kernels carry; `roofline`, `kernels` and `cpu_baseline` are null.  --full adds, after the timed region:
+`roofline` = the dominant kernel of the workload, its launches timed live with HIP events on the launch
+stream (a second, eager pass of the K steps when the timed steps replay a graph), with the board's
+sustained matrix-pipe rate and, on the default call, counter passes of its own; `cpu_baseline` = the CPU
+oracle on a bounded sample on this host (rank 0, N = 1 only); the dense-stem and reduced-precision A/Bs;
+per-rank figures (`ranks`); and, on the default call, BASELINE.json's other GPU configurations.
 """
 import argparse
 import json
@@ -302,7 +308,7 @@ def run_other_configs():
     import subprocess
     res = {}
     for label, flags in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--child'] + flags
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--child', '--full'] + flags
         t0 = time.perf_counter()
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
@@ -457,7 +463,7 @@ def main():
                          'fp16 (narrower than fp32: opt-in A/B only, reported beside the headline under "reduced_precision_modes")')
     ap.add_argument('--smpl-kernel', default='auto', choices=['auto', 'wide', 'narrow'],
                     help='smpl workload, fp16x3_lbs* modes: auto = by batch size (64-body workgroups from 2048 bodies on), wide / narrow = force one (A/B)')
-    ap.add_argument('--no-reduced-ab', action='store_true', help='smpl workload: skip the extra timed pass of the reduced-precision p16 mode')
+    ap.add_argument('--no-reduced-ab', action='store_true', help='--full, smpl workload: skip the extra timed pass of the reduced-precision p16 mode')
     ap.add_argument('--conv-precision', default='bf16x3', choices=['fp32', 'bf16x3'],
                     help="encoder convolutions (forward + data gradient): 'fp32' = exact-fp32 MFMA chain, 'bf16x3' = three bf16 planes per fp32 "
                          "operand, six products per term, fp32 accumulate (same accuracy class, bf16 matrix pipe)")
@@ -473,7 +479,11 @@ def main():
     ap.add_argument('--exchange-backend', default='torch', choices=['torch', 'rccl'],
                     help="gradient exchange through torch.distributed ('torch': the nccl backend == RCCL) or through the library's own C ABI "
                          "('rccl': straps_comm_* / straps_allreduce_grads on a dedicated stream)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what the headline does not need: roofline and per-kernel figures (an eager pass of the '
+                         'steps when they replay a graph), the CPU baseline, the dense-stem and reduced-precision A/Bs, per-rank figures and, on the '
+                         "default call, counter passes and BASELINE.json's other GPU configurations")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of replaying a captured hipGraph')
     ap.add_argument('--dense-stem', action='store_true', help='A/B: disable the exact zero skipping of the stem (treat every input cell as non-zero)')
     ap.add_argument('--no-overlap', action='store_true', help='(default now) weight-gradient kernels stay on the main stream')
@@ -482,23 +492,25 @@ def main():
     ap.add_argument('--no-x3f-operand-bn', action='store_true', help="A/B: the BatchNorm in front of a fp32-operand 1x1 layer as an apply pass instead of in the operand path")
     ap.add_argument('--no-x3f', action='store_true', help="A/B: the long 1x1 layers on the plane route (rounds 2-5) instead of the fp32-operand route (csrc/conv_x3f.hip)")
     ap.add_argument('--no-relu-bits', action='store_true', help="A/B: a residual unit's ReLU decisions reach the backward pass as fp32 tensors (rounds 1-3) instead of bits")
-    ap.add_argument('--no-stem-ab', action='store_true', help='skip the dense-stem A/B steps after the timed region (profiling runs: keeps the kernel stats clean)')
+    ap.add_argument('--no-stem-ab', action='store_true', help='--full: skip the dense-stem A/B steps after the timed region')
     ap.add_argument('--overlap-wgrad', action='store_true', help='A/B: run the weight-gradient kernels on a side stream (0.1 ms slower since the data pipeline)')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help="default headline run only: skip the short timed passes of BASELINE.json's other GPU configurations (configs[1], configs[3]'s "
+                    help="--full, default headline run only: skip the short timed passes of BASELINE.json's other GPU configurations (configs[1], configs[3]'s "
                          "per-GPU shape, configs[4]) that are reported under 'other_configs'")
     ap.add_argument('--measure-traffic', action='store_true',
                     help="measure roofline.traffic in this run (two short rocprofv3 counter passes after the timed region) instead of reading the "
-                         "committed profiles/pmc_traffic.json; on by default for the driver-style default call")
+                         "committed profiles/pmc_traffic.json; implies --full, on by default for the default call with --full")
     ap.add_argument('--no-measure-traffic', action='store_true')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; rank 0; "
                          "a fixed, seeded sample of bodies / parameters where the outputs exceed 64 MB)")
     ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)      # (a pass launched by the headline run for 'other_configs')
     args = ap.parse_args()
-    # the driver's one call (no --workload / --config / --layers / --batch) also times the other GPU configurations, each in a child process of
-    # its own after the headline ("make the driver's one bench call carry every GPU config")
-    headline_default = (args.workload == 'train' and not args.config and args.layers == 18 and not args.batch and not args.child
+    if args.measure_traffic:
+        args.full = True
+    # the default call with --full (no --workload / --config / --layers / --batch) also times the other GPU configurations, each in a child
+    # process of its own after the headline, and measures the dominant kernel's traffic with counter passes of its own
+    headline_default = (args.full and args.workload == 'train' and not args.config and args.layers == 18 and not args.batch and not args.child
                         and args.conv_precision == 'bf16x3' and not args.dense_stem and not args.no_graph and not args.no_cpu_baseline)
     if args.child:
         args.no_cpu_baseline = args.no_stem_ab = args.no_reduced_ab = True
@@ -671,14 +683,19 @@ def main():
         else:
             outs = graph_out if graph_mode else last_out
         dump_outputs(args.dump_outputs, outs, B)
+    if dist is not None:               # (the whole job's time: the slowest rank's)
+        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    # everything from here to the result line beyond what `value` / `ms_per_step` need runs with --full only
     exposed_exchange_ms = None
     if args.workload == 'train':
         ts.time_exchange = False
-        if ts.exchange_events:
+        if args.full and ts.exchange_events:
             exposed_exchange_ms = sum(a.elapsed_time(b) for a, b in ts.exchange_events) / len(ts.exchange_events)
     graph_captured = args.workload != 'train' or ts.graph is not None
     eager_ms, eager_sclk_mhz = None, None
-    if graph_mode:
+    if args.full and graph_mode:
         # same K steps launched eagerly with HIP-event pairs around the MFMA kernels (roofline section)
         if args.workload == 'train':
             ts.use_graph = False
@@ -698,7 +715,7 @@ def main():
     # A/B inside the same run: the stem kernels with their exact zero skipping defeated (every input cell marked non-zero = the
     # plain dense convolution), 3 eager steps on every rank (the step's all-reduce is collective)
     stem_ab = None
-    if args.workload == 'train' and not args.dense_stem and not args.no_stem_ab:
+    if args.full and args.workload == 'train' and not args.dense_stem and not args.no_stem_ab:
         if ts.use_graph:
             ts.use_graph, ts.side_stream, ts.pipeline = False, None, False
         saved, timer.recs = timer.recs, []
@@ -715,7 +732,7 @@ def main():
         reg.image_encoder.dense_stem = False
         stem_ab = {k: dense[k][2] / 3 * 1e3 for k in ('stem_kernel', 'stem_wgrad_kernel') if k in dense}
     reduced = None
-    if args.workload == 'smpl' and smpl_precision == 'fp16x3_lbs' and not args.no_reduced_ab:
+    if args.full and args.workload == 'smpl' and smpl_precision == 'fp16x3_lbs' and not args.no_reduced_ab:
         # the pose-corrective blend in plain fp16 (narrower than the reference's fp32; inside north_star's 1e-4 m): NOT the headline --
         # the same K steps timed again and reported beside it
         def step_p16():
@@ -731,11 +748,7 @@ def main():
         reduced = {'fp16x3_lbs_p16': {'value': round(B * args.steps / dt2, 1), 'unit': 'bodies/s (this rank)', 'ms_per_step': round(dt2 / args.steps * 1e3, 4),
                                       'launch_mode': 'eager', 'note': 'pose-corrective blend as ONE plain-fp16 product per term: reduced precision, opt-in'}}
     rank_ms = None
-    if dist is not None or (args.workload == 'train' and args.force_exchange):
-        if dist is not None:
-            t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            elapsed = float(t.item())
+    if args.full and (dist is not None or (args.workload == 'train' and args.force_exchange)):
         # per-rank view: each rank's own time to finish its K steps (before the closing barrier) and the part of the gradient
         # exchange its backward did not hide
         # (+ a digest of this replica's parameters after the timed steps: data parallelism keeps the replicas bit-identical, and a corrupted
@@ -782,7 +795,7 @@ def main():
     out = None
     if rank == 0:
         bodies = B * args.steps * world
-        agg = timer.summary()
+        agg = timer.summary() if args.full else {}
         roof = None
         if dominant in agg:
             n, flops, secs, abytes = agg[dominant]
@@ -857,7 +870,7 @@ def main():
                 others[k]['tflops_dense_equivalent'] = others[k].pop('tflops')
                 others[k]['zero_skipping'] = True
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args, mp, smpl_model, (smpl, smpl_precision) if args.workload == 'smpl' else None)
         out = {'metric': 'bodies/sec', 'value': round(bodies / elapsed, 1), 'unit': 'bodies/s', 'n_gpus': world,
                'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 4),
@@ -867,7 +880,7 @@ def main():
                'config': {'workload': workload, 'bodies_per_gpu_per_step': B, 'global_batch': B * world,
                           'input': 'theta(24x3x3), beta(10)' if args.workload == 'smpl' else '18x256x256 fp32 NCHW proxy built on the device by the step itself (rendered part silhouette + 17 joint heat-maps, ~98 % exact zeros as in the reference pipeline)',
                           'parallelism': par},
-               'roofline': roof, 'kernels': others, 'cpu_baseline': cpu,
+               'roofline': roof, 'kernels': others if args.full else None, 'cpu_baseline': cpu,
                'sclk_mhz': sclk_mhz, 'sclk_note': 'shader clock the implicit-GEMM convolution kernels ran at over the timed region (s_memtime / s_memrealtime '
                                                   'ticks of workgroup 0 of every launch; spec 2400; null for workloads without convolutions): the chip clocks '
                                                   'to its power budget, boards differ by several per cent'}

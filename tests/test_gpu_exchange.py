@@ -105,7 +105,7 @@ def test_train_step_with_the_exchange_forced_on_rccl_world_one():
 
 @pytest.mark.parametrize('backend', ['torch', 'rccl'])
 def test_bench_line_with_the_exchange_forced_at_one_rank(backend):
-    """`python bench.py --gpus 1 --force-exchange --exchange-backend torch|rccl`: the code path of the first multi-GPU run
+    """`python bench.py --gpus 1 --full --force-exchange --exchange-backend torch|rccl`: the code path of the first multi-GPU run
     -- split hipGraphs, tail bucket on RCCL under the rest of backward, head bucket, Adam -- driver-visible on a one-GPU box: the bench line carries
     ranks.exposed_exchange_ms_*, ranks.replicas_in_sync and which backend ran."""
     import json
@@ -114,7 +114,7 @@ def test_bench_line_with_the_exchange_forced_at_one_rank(backend):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '3', '--force-exchange', '--exchange-backend', backend,
-           '--no-cpu-baseline', '--no-other-configs', '--no-measure-traffic', '--no-stem-ab']
+           '--full', '--no-cpu-baseline', '--no-other-configs', '--no-measure-traffic', '--no-stem-ab']
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]

@@ -164,7 +164,7 @@ def test_bench_launched_the_way_the_driver_launches_it_two_ranks():
     env = dict(os.environ, STRAPS_FORCE_DEVICE='0', STRAPS_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     port = 29900 + os.getpid() % 90
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port', str(port),
-           os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2']
+           os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--full']
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]

@@ -7,6 +7,6 @@ if [ -n "$2" ]; then
   tail -6 $O/pytest.log
 fi
 for i in 1 2; do
-  env $1 timeout 200 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$1 ', j['value'], j['ms_per_step'], j['kernels'].get('stem_wgrad_kernel'))"
-  timeout 200 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('default', j['value'], j['ms_per_step'], j['kernels'].get('stem_wgrad_kernel'))"
+  env $1 timeout 200 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$1 ', j['value'], j['ms_per_step'], j['kernels'].get('stem_wgrad_kernel'))"
+  timeout 200 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('default', j['value'], j['ms_per_step'], j['kernels'].get('stem_wgrad_kernel'))"
 done

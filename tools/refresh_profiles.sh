@@ -31,11 +31,11 @@ pmc smpl_r18_b65536_fp16x3_lbs_p16 smpl_65536_p16 "$S --workload smpl --smpl-pre
 pmc train_r50_b32 train_r50_b32 "$S --config 3 --steps 2 --warmup 1 --no-graph; tools/refresh_profiles.sh" --config 3 --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-overlap --no-stem-ab
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json      # bench.py reports roofline.traffic from this file
 cd $R
-python bench.py 2>/dev/null | tail -1 > $O/${RND}_bench_train_b64.json
-python bench.py --conv-precision fp32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${RND}_bench_train_b64_fp32conv.json
-python bench.py --config 1 2>/dev/null | tail -1 > $O/${RND}_bench_fwd_b64.json
-python bench.py --config 4 2>/dev/null | tail -1 > $O/${RND}_bench_smpl_1M.json
-python bench.py --config 4 --smpl-precision fp32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${RND}_bench_smpl_1M_fp32.json
-python bench.py --config 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${RND}_bench_train_r50_b32.json
+python bench.py --full 2>/dev/null | tail -1 > $O/${RND}_bench_train_b64.json
+python bench.py --full --conv-precision fp32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${RND}_bench_train_b64_fp32conv.json
+python bench.py --full --config 1 2>/dev/null | tail -1 > $O/${RND}_bench_fwd_b64.json
+python bench.py --full --config 4 2>/dev/null | tail -1 > $O/${RND}_bench_smpl_1M.json
+python bench.py --full --config 4 --smpl-precision fp32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${RND}_bench_smpl_1M_fp32.json
+python bench.py --full --config 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${RND}_bench_train_r50_b32.json
 rm -rf $O/prof_*/ $O/pmc_*/
 ls -la $O
