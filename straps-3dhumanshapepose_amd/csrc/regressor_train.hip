@@ -8,72 +8,40 @@
 // descriptor table into the workspace: the table lives in the kernel arguments, so nothing is copied from host memory and a
 // fwd_train + bwd pair can be captured into a hipGraph.
 //
-// A Plan walks the network once per call: the flat parameter / running-statistic offsets, every layer's route (fp32-operand 1x1,
+// A Plan adds to the network walk and geometry of regressor_net.h, for one (batch, h, w): every layer's route (fp32-operand 1x1,
 // bf16x3 planes, fp32), which forms of each activation the module materialises, and the workspace offsets of the tape and of the
 // backward's reused slots.
 #include <algorithm>
 #include <cstring>
 
-#include "common.h"
+#include "regressor_net.h"
 
 namespace {
 
-constexpr int kEstLd = 160;           // IEF estimate row stride (ief_module.EST_LD)
-constexpr int kNumParams = 157;       // cam 3 | pose 24 x 6 | shape 10
-constexpr float kBnEps = 1e-5f;       // nn.BatchNorm2d defaults
-constexpr float kBnMomentum = 0.1f;
-constexpr size_t kAlign = 256;
-constexpr int kMaxConvs = 56;         // resnet50 has 52 convolutions besides the stem
 constexpr long long kX3fMinRows = 16384;    // encoder_exec.X3F_MIN_ROWS
 constexpr size_t kNone = ~(size_t)0;        // "this form of a tensor is not materialised"
 
-size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
-long long round8(long long v) { return (v + 7) / 8 * 8; }
-int conv_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
-
-struct Conv {
-    int cin, cout, k, stride, pad;
-    long long w_off, gb_off;          // params: OIHW weight; gamma then beta
-    long long rs_off;                 // bn_state: running_mean then running_var
-    long long first;                  // element offset in the packed weights (ResNet.prepack's order)
-    long long inf_w, inf_bn;          // the same tensors in the inference layout (straps_regressor_param_floats)
-    // ---- per (batch, h, w) ----
-    int H, W, Ho, Wo;                 // input / output extent
+// one convolution with its training route, tensor forms and tape
+struct Layer : Conv, Extent {
     long long rows;                   // batch * Ho * Wo
     bool fmode;                       // fp32-operand route (encoder_exec.x3f_mode)
-    bool relu, last;                  // ReLU after the BatchNorm; last convolution of a unit
     bool keep, planes, defer, bits;   // output forms: fp32, planes, BatchNorm deferred into the consumer, ReLU bits
     bool keep_grad;                   // autograd_ops keep(): does anything read the fp32 gradient of the raw output
     int nblk;                         // forward statistics blocks
     // input activation (workspace offsets; kNone = not materialised) and the deferred BatchNorm applied in the operand path
     size_t x, x3;
     long long x_ps;
-    const Conv* a_bn;
+    const Layer* a_bn;
     // tape
     size_t raw, ss, out, out3, bitsb;
     long long out_ps;
 };
 
-struct Unit {
-    Conv c[3];
-    int nconv;
-    bool has_ds;
-    Conv dsc;
-};
-
-struct Plan {
-    int layers, cin, iters, x3;
-    int F, H1, H2;
-    long long stem_w, stem_gb, stem_rs, inf_stem_w, inf_stem_bn;
-    Unit units[16];
-    int nunits;
-    Conv* convs[kMaxConvs];           // non-stem convolutions in parameter order
-    int nconvs;
-    long long conv_total, ps;
-    long long fc1w, fc1b, fc2w, fc2b, fc3w, fc3b, param_floats, bn_floats;
-    long long inf_fc1w, inf_init;
-    // ---- per (batch, h, w): geometry ----
-    int B, Hs, Ws, Hp, Wp, Hf, Wf, stem_nblk;
+struct Plan : Net {
+    bool x3;
+    int B, stem_nblk;
+    Geometry geo;
+    Layer lay[kMaxConvs];             // Net::convs with their training state
     bool pool_planes;
     long long amax;                   // largest activation / raw output (elements)
     // workspace (bytes): packed weights, tape, forward scratch, backward slots
@@ -83,100 +51,30 @@ struct Plan {
     size_t feat, c1, ests, h1s, h2s, fpart;
     size_t g[2], dz, dskip, dt, draw, draw3, drawd, drawd3, part, bnws, wgws, tact, sdraw, swgws, dgb, dests, dh2s, dh1s, dc1, dfeat;
     size_t bytes;
+    const Layer& unit_out(int ui) const { return lay[units[ui].c[units[ui].nconv - 1]]; }      // a unit's last convolution
 };
 
-const char* check_desc(const straps_regressor_desc_t* d) {
-    if (!d) return "null pointer `desc`";
-    if (d->layers != 18 && d->layers != 50) return "`layers` must be 18 or 50";
-    if (d->in_channels < 1 || d->in_channels > 256) return "`in_channels` must be in [1, 256]";
-    if (d->ief_iters < 1 || d->ief_iters > 64) return "`ief_iters` must be in [1, 64]";
-    // (3 = bf16 is an inference-only route: straps_regressor_fwd_infer; no train entry point accepts it)
-    if (d->precision != 0 && d->precision != 1) return "`precision` must be 0 (bf16x3) or 1 (fp32) for training (3 = bf16 is inference-only)";
-    return nullptr;
-}
-
-// parameter layouts: regressor.parameters() (train), running statistics in module order, state_dict() + initial estimate (inference)
-void make_layout(const straps_regressor_desc_t* d, Plan& p) {
-    p.layers = d->layers;
-    p.cin = d->in_channels;
-    p.iters = d->ief_iters;
-    p.x3 = d->precision == 0;
-    const bool bottleneck = d->layers == 50;
-    const int blocks18[4] = {2, 2, 2, 2}, blocks50[4] = {3, 4, 6, 3};
-    const int* blocks = bottleneck ? blocks50 : blocks18;
-    const int expansion = bottleneck ? 4 : 1;
-    long long off = 0, rs = 0, inf = 0, first = 0;
-    p.nconvs = 0;
-    p.nunits = 0;
-    auto conv = [&](Conv& cv, int cin, int cout, int k, int stride, int pad) {
-        cv.cin = cin; cv.cout = cout; cv.k = k; cv.stride = stride; cv.pad = pad;
-        const long long n = (long long)cout * cin * k * k;
-        cv.w_off = off; cv.gb_off = off + n; off += n + 2LL * cout;
-        cv.rs_off = rs; rs += 2LL * cout;
-        cv.inf_w = inf; cv.inf_bn = inf + n; inf += n + 4LL * cout;
-        cv.first = first; first += n;
-        p.convs[p.nconvs++] = &cv;
-    };
-    p.stem_w = off; p.stem_gb = off + 64LL * p.cin * 49; off = p.stem_gb + 128;
-    p.stem_rs = rs; rs += 128;
-    p.inf_stem_w = inf; p.inf_stem_bn = inf + 64LL * p.cin * 49; inf = p.inf_stem_bn + 256;
-    int inplanes = 64;
-    for (int li = 0; li < 4; ++li) {
-        const int planes = 64 << li, stride = li == 0 ? 1 : 2;
-        for (int bi = 0; bi < blocks[li]; ++bi) {
-            Unit& u = p.units[p.nunits++];
-            const int s = bi == 0 ? stride : 1, outp = planes * expansion;
-            if (bottleneck) {
-                u.nconv = 3;
-                conv(u.c[0], inplanes, planes, 1, 1, 0);
-                conv(u.c[1], planes, planes, 3, s, 1);
-                conv(u.c[2], planes, outp, 1, 1, 0);
-            } else {
-                u.nconv = 2;
-                conv(u.c[0], inplanes, planes, 3, s, 1);
-                conv(u.c[1], planes, planes, 3, 1, 1);
-            }
-            u.has_ds = bi == 0 && (s != 1 || inplanes != outp);
-            if (u.has_ds) conv(u.dsc, inplanes, outp, 1, s, 0);
-            for (int ci = 0; ci < u.nconv; ++ci) { u.c[ci].relu = true; u.c[ci].last = ci == u.nconv - 1; }
-            u.dsc.relu = false; u.dsc.last = false;
-            inplanes = outp;
-        }
-    }
-    p.conv_total = first;
-    p.ps = round8(first);
-    p.F = inplanes;
-    p.H1 = p.H2 = bottleneck ? 1024 : 512;
-    p.fc1w = off; off += (long long)p.H1 * (p.F + kNumParams);
-    p.fc1b = off; off += p.H1;
-    p.fc2w = off; off += (long long)p.H2 * p.H1;
-    p.fc2b = off; off += p.H2;
-    p.fc3w = off; off += (long long)kNumParams * p.H2;
-    p.fc3b = off; off += kNumParams;
-    p.param_floats = off;
-    p.bn_floats = rs;
-    p.inf_fc1w = inf;
-    p.inf_init = inf + (off - p.fc1w);
-}
-
-bool x3f_mode(const Plan& p, const Conv& cv, int H, int W) {
+bool x3f_mode(const Plan& p, const Layer& cv) {
     if (!p.x3 || !straps_conv_x3f_supported(cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad)) return false;
-    return (long long)p.B * conv_out(H, cv.k, cv.stride, cv.pad) * conv_out(W, cv.k, cv.stride, cv.pad) >= kX3fMinRows;
+    return (long long)p.B * cv.Ho * cv.Wo >= kX3fMinRows;
 }
 
 // (fp32, planes) forms an activation must exist in for the convolution that reads it (encoder_exec._residual_stages.needs)
-void needs(const Plan& p, const Conv& cv, int H, int W, bool& f32, bool& planes) {
-    if (x3f_mode(p, cv, H, W)) { f32 = true; planes = false; return; }
-    f32 = !straps_conv_wgrad_x3_on_planes(p.B, H, W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad);
+void needs(const Plan& p, const Layer& cv, bool& f32, bool& planes) {
+    if (x3f_mode(p, cv)) { f32 = true; planes = false; return; }
+    f32 = !straps_conv_wgrad_x3_on_planes(p.B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad);
     planes = true;
 }
 
-// routes, tensor forms and workspace offsets for one (batch, h, w); false if the input is too small for the network
+// routes, tensor forms and workspace offsets for one (batch, h, w) on top of make_net; false if the input is too small for the network
 bool make_plan(Plan& p, int B, int H, int W) {
-    if (B <= 0 || H < 7 || W < 7) return false;
+    if (!make_geometry(p, B, H, W, p.geo)) return false;
+    p.x3 = p.precision == 0;
     p.B = B;
-    p.Hs = conv_out(H, 7, 2, 3); p.Ws = conv_out(W, 7, 2, 3);
-    p.Hp = conv_out(p.Hs, 3, 2, 1); p.Wp = conv_out(p.Ws, 3, 2, 1);
+    for (int i = 0; i < p.nconvs; ++i) {
+        static_cast<Conv&>(p.lay[i]) = p.convs[i];
+        static_cast<Extent&>(p.lay[i]) = p.geo.e[i];
+    }
     size_t b = 0;
     auto take = [&](size_t bytes) { const size_t o = b; b = align_up(b + (bytes ? bytes : 1)); return o; };
     auto f32s = [&](long long n) { return take((size_t)n * sizeof(float)); };
@@ -192,7 +90,7 @@ bool make_plan(Plan& p, int B, int H, int W) {
     p.w1e = f32s((long long)p.H1 * kEstLd);
     p.w3 = f32s((long long)(kNumParams + 31) / 32 * 32 * p.H2);
     // ---- stem tape ----
-    const long long stem_n = (long long)B * p.Hs * p.Ws * 64, pool_n = (long long)B * p.Hp * p.Wp * 64;
+    const long long stem_n = (long long)B * p.geo.Hs * p.geo.Ws * 64, pool_n = (long long)B * p.geo.Hp * p.geo.Wp * 64;
     p.nz = take(straps_stem_nzmask_words(B, p.cin, H, W) * sizeof(uint32_t));
     p.stem_raw = f32s(stem_n);
     p.stem_ss = f32s(4 * 64);
@@ -203,7 +101,7 @@ bool make_plan(Plan& p, int B, int H, int W) {
     p.amax = pool_n;
     {   // the pooled output's planes unless every reader takes the fp32 tensor (encoder_forward)
         const Unit& u0 = p.units[0];
-        bool all = x3f_mode(p, u0.c[0], p.Hp, p.Wp) && (!u0.has_ds || x3f_mode(p, u0.dsc, p.Hp, p.Wp));
+        bool all = x3f_mode(p, p.lay[u0.c[0]]) && (!u0.has_ds || x3f_mode(p, p.lay[u0.ds]));
         p.pool_planes = p.x3 && !all;
         p.pool3 = p.pool_planes ? planes(pool_n) : kNone;
         p.pool_ps = p.pool_planes ? round8(pool_n) : 0;
@@ -212,13 +110,10 @@ bool make_plan(Plan& p, int B, int H, int W) {
     long long part_d = 1, bnws = straps_bn_bwd_workspace_bytes(stem_n, 64), wgws = 4;
     size_t in = p.pool, in3 = p.pool3;
     long long in_ps = p.pool_ps;
-    int h = p.Hp, w = p.Wp;
-    auto geometry = [&](Conv& cv, int ch, int cw) -> bool {
-        cv.H = ch; cv.W = cw;
-        cv.Ho = conv_out(ch, cv.k, cv.stride, cv.pad); cv.Wo = conv_out(cw, cv.k, cv.stride, cv.pad);
-        if (cv.Ho <= 0 || cv.Wo <= 0) return false;
+    auto tape = [&](Layer& cv) -> bool {
+        const int ch = cv.H, cw = cv.W;
         cv.rows = (long long)B * cv.Ho * cv.Wo;
-        cv.fmode = x3f_mode(p, cv, ch, cw);
+        cv.fmode = x3f_mode(p, cv);
         cv.nblk = cv.fmode ? straps_conv_x3f_stat_blocks(B, ch, cw, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0)
                  : p.x3    ? straps_conv_x3_stat_blocks(B, ch, cw, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0)
                            : straps_conv_stat_blocks(B, cv.Ho, cv.Wo, cv.cout, cv.k * cv.k * cv.cin, 0);
@@ -239,34 +134,33 @@ bool make_plan(Plan& p, int B, int H, int W) {
         return true;
     };
     for (int ui = 0; ui < p.nunits; ++ui) {
-        Unit& u = p.units[ui];
+        const Unit& u = p.units[ui];
         if (u.has_ds) {     // projection: BatchNorm without ReLU, fp32 output (the identity)
-            Conv& cv = u.dsc;
-            if (!geometry(cv, h, w)) return false;
+            Layer& cv = p.lay[u.ds];
+            if (!tape(cv)) return false;
             cv.x = in; cv.x3 = in3; cv.x_ps = in_ps; cv.a_bn = nullptr;
             cv.keep = true; cv.planes = false; cv.defer = false; cv.bits = false;
             cv.out = f32s(cv.rows * cv.cout); cv.out3 = kNone; cv.out_ps = 0; cv.bitsb = kNone;
         }
         size_t t = in, t3 = in3;
         long long t_ps = in_ps;
-        const Conv* a_bn = nullptr;
-        int th = h, tw = w;
+        const Layer* a_bn = nullptr;
         for (int ci = 0; ci < u.nconv; ++ci) {
-            Conv& cv = u.c[ci];
-            if (!geometry(cv, th, tw)) return false;
+            Layer& cv = p.lay[u.c[ci]];
+            if (!tape(cv)) return false;
             cv.x = t; cv.x3 = t3; cv.x_ps = t_ps; cv.a_bn = a_bn;
             bool keep = true, pl = true, defer = false;
             if (p.x3 && !cv.last) {
-                needs(p, u.c[ci + 1], cv.Ho, cv.Wo, keep, pl);
+                needs(p, p.lay[u.c[ci + 1]], keep, pl);
                 defer = keep && !pl;
             } else if (p.x3) {
                 pl = false;
                 if (ui + 1 < p.nunits) {
                     const Unit& nx = p.units[ui + 1];
                     bool f, q;
-                    needs(p, nx.c[0], cv.Ho, cv.Wo, f, q);
+                    needs(p, p.lay[nx.c[0]], f, q);
                     pl = q;
-                    if (nx.has_ds) { needs(p, nx.dsc, cv.Ho, cv.Wo, f, q); pl = pl || q; }
+                    if (nx.has_ds) { needs(p, p.lay[nx.ds], f, q); pl = pl || q; }
                 }
             }
             cv.defer = defer;
@@ -285,17 +179,14 @@ bool make_plan(Plan& p, int B, int H, int W) {
                 cv.bitsb = cv.bits ? take((size_t)cv.rows * (cv.cout / 32) * sizeof(uint32_t)) : kNone;
                 t = cv.out; t3 = cv.out3; t_ps = cv.out_ps; a_bn = nullptr;
             }
-            th = cv.Ho; tw = cv.Wo;
         }
-        h = th; w = tw;
         in = t; in3 = t3; in_ps = t_ps;
     }
     // autograd_ops.encoder_backward keep(): the fp32 gradient of a raw output is needed unless its weight gradient runs on planes
     for (int i = 0; i < p.nconvs; ++i) {
-        Conv& cv = *p.convs[i];
+        Layer& cv = p.lay[i];
         cv.keep_grad = !p.x3 || cv.fmode || !straps_conv_wgrad_x3_on_planes(B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad);
     }
-    p.Hf = h; p.Wf = w;
     p.feat = f32s((long long)B * p.F);
     p.c1 = f32s((long long)B * p.H1);
     p.ests = f32s((long long)(p.iters + 1) * B * kEstLd);
@@ -339,12 +230,6 @@ __global__ __launch_bounds__(64) void write_table_kernel(PackTable t, int n, str
     if (i == 0) *one = 1.0f;
 }
 
-#define RT_CALL(expr)                         \
-    do {                                      \
-        const int rc__ = (expr);              \
-        if (rc__ != STRAPS_OK) return rc__;   \
-    } while (0)
-
 struct Ws {
     char* base;
     float* f(size_t off) const { return off == kNone ? nullptr : (float*)(base + off); }
@@ -352,26 +237,19 @@ struct Ws {
     unsigned* u(size_t off) const { return off == kNone ? nullptr : (unsigned*)(base + off); }
 };
 
-// the argument checks fwd_train and bwd share; also walks the plan for this input
+// the argument checks fwd_train and bwd share beyond check_args; also walks the plan for this input
 int check_common(const char* fn, const straps_regressor_desc_t* d, const float* params, const float* x, int batch, int h, int w,
                  const void* workspace, Plan& p) {
-    const char* bad = check_desc(d);
-    STRAPS_REQUIRE(!bad, "%s: %s", fn, bad);
+    RG_CALL(check_args(fn, d, true, x, batch, h, w, workspace));
     STRAPS_REQUIRE(params, "%s: null pointer `params`", fn);
-    STRAPS_REQUIRE(x, "%s: null pointer `x`", fn);
-    STRAPS_REQUIRE(workspace, "%s: null pointer `workspace`", fn);
-    STRAPS_REQUIRE(batch >= 1, "%s: `batch` must be positive (got %d)", fn, batch);
-    STRAPS_REQUIRE(h >= 7 && w >= 7, "%s: `h` and `w` must be at least 7 (got %d x %d)", fn, h, w);
     STRAPS_REQUIRE(((uintptr_t)params & 15) == 0, "%s: `params` must be 16-byte aligned", fn);
-    STRAPS_REQUIRE(((uintptr_t)workspace & (kAlign - 1)) == 0, "%s: `workspace` must be %zu-byte aligned", fn, kAlign);
-    STRAPS_REQUIRE(((uintptr_t)x & 3) == 0, "%s: `x` must be float-aligned", fn);
-    make_layout(d, p);
+    make_net(d, p);
     STRAPS_REQUIRE(make_plan(p, batch, h, w), "%s: input %d x %d is too small for resnet%d", fn, h, w, p.layers);
     return STRAPS_OK;
 }
 
-int finalize(const Plan& p, const float* params, float* bn_state, const float* part, int nblk, int c, long long rows, long long gb, long long rs,
-             float* ss, hipStream_t st) {
+int finalize(const float* params, float* bn_state, const float* part, int nblk, int c, long long rows, long long gb, long long rs, float* ss,
+             hipStream_t st) {
     return straps_bn_stats_finalize(part, nblk, c, rows, params + gb, params + gb + c, kBnEps, kBnMomentum, bn_state + rs, bn_state + rs + c,
                                     ss, ss + c, ss + 2 * c, ss + 3 * c, st);
 }
@@ -379,23 +257,23 @@ int finalize(const Plan& p, const float* params, float* bn_state, const float* p
 }  // namespace
 
 extern "C" size_t straps_regressor_train_param_floats(const straps_regressor_desc_t* d) {
-    if (check_desc(d)) return 0;
-    Plan p;
-    make_layout(d, p);
-    return (size_t)p.param_floats;
+    if (check_desc(d, true)) return 0;
+    Net n;
+    make_net(d, n);
+    return (size_t)n.train_floats;
 }
 
 extern "C" size_t straps_regressor_bn_state_floats(const straps_regressor_desc_t* d) {
-    if (check_desc(d)) return 0;
-    Plan p;
-    make_layout(d, p);
-    return (size_t)p.bn_floats;
+    if (check_desc(d, true)) return 0;
+    Net n;
+    make_net(d, n);
+    return (size_t)n.bn_floats;
 }
 
 extern "C" size_t straps_regressor_train_workspace_bytes(const straps_regressor_desc_t* d, int batch, int h, int w) {
-    if (check_desc(d)) return 0;
+    if (check_desc(d, true)) return 0;
     Plan p;
-    make_layout(d, p);
+    make_net(d, p);
     if (!make_plan(p, batch, h, w)) return 0;
     return p.bytes;
 }
@@ -405,7 +283,7 @@ extern "C" int straps_regressor_fwd_train(const straps_regressor_desc_t* d, cons
                                           size_t workspace_bytes, void* stream) {
     static const char* fn = "straps_regressor_fwd_train";
     Plan p;
-    RT_CALL(check_common(fn, d, params, x, batch, h, w, workspace, p));
+    RG_CALL(check_common(fn, d, params, x, batch, h, w, workspace, p));
     STRAPS_REQUIRE(bn_state, "%s: null pointer `bn_state`", fn);
     STRAPS_REQUIRE(init_est, "%s: null pointer `init_est`", fn);
     STRAPS_REQUIRE(est, "%s: null pointer `est`", fn);
@@ -416,17 +294,17 @@ extern "C" int straps_regressor_fwd_train(const straps_regressor_desc_t* d, cons
                    workspace_bytes, p.bytes);
     hipStream_t st = (hipStream_t)stream;
     const Ws ws{(char*)workspace};
-    const int B = batch, C = p.cin, F = p.F, H1 = p.H1, H2 = p.H2, T = p.iters;
+    const int B = batch, C = p.cin, F = p.F, H1 = p.H1, H2 = p.H2;
     const bool x3 = p.x3;
     unsigned short* krsc3 = ws.h(p.krsc);
     float* krsc = ws.f(p.krsc);
 
     // ---- weights: the stem's fragment order, every convolution in one batched pack (ResNet.prepack, both layouts), the IEF packing ----
-    RT_CALL(straps_pack_stem_weight(params + p.stem_w, ws.f(p.wstem), C, stream));
+    RG_CALL(straps_pack_stem_weight(params + p.stem.w_off, ws.f(p.wstem), C, stream));
     PackTable tbl;
     memset(&tbl, 0, sizeof(tbl));
     for (int i = 0; i < p.nconvs; ++i) {
-        const Conv& cv = *p.convs[i];
+        const Conv& cv = p.convs[i];
         straps_pack_desc_t& e = tbl.d[i];
         e.src = params + cv.w_off;
         e.dst_krsc = x3 ? nullptr : ws.f(p.krsc) + cv.first;
@@ -437,25 +315,25 @@ extern "C" int straps_regressor_fwd_train(const straps_regressor_desc_t* d, cons
     straps_pack_desc_t* table = (straps_pack_desc_t*)(ws.base + p.table);
     hipLaunchKernelGGL(write_table_kernel, dim3(1), dim3(64), 0, st, tbl, p.nconvs, table, ws.f(p.one));
     STRAPS_CHECK_LAUNCH("write_table_kernel");
-    if (x3) RT_CALL(straps_pack_conv_weights_batched_x3(table, p.nconvs, p.conv_total, krsc3, ws.h(p.crsk), p.ps, stream));
-    else RT_CALL(straps_pack_conv_weights_batched(table, p.nconvs, p.conv_total, stream));
-    RT_CALL(straps_ief_pack(params + p.fc1w, params + p.fc3w, ws.f(p.w1f), ws.f(p.w1e), ws.f(p.w3), F, kNumParams, H1, H2, kEstLd, stream));
+    if (x3) RG_CALL(straps_pack_conv_weights_batched_x3(table, p.nconvs, p.conv_total, krsc3, ws.h(p.crsk), p.ps, stream));
+    else RG_CALL(straps_pack_conv_weights_batched(table, p.nconvs, p.conv_total, stream));
+    RG_CALL(straps_ief_pack(params + p.ief.fc1w, params + p.ief.fc3w, ws.f(p.w1f), ws.f(p.w1e), ws.f(p.w3), F, kNumParams, H1, H2, kEstLd, stream));
 
     // ---- stem: raw conv + statistics, BatchNorm + ReLU + max pool in one pass (encoder_forward with a tape) ----
     uint32_t* nz = (uint32_t*)(ws.base + p.nz);
     float* part = ws.f(p.fpart);
     float* sss = ws.f(p.stem_ss);
-    RT_CALL(straps_stem_nzmask(x, nz, B, C, h, w, stream));
-    RT_CALL(straps_stem_fwd(x, ws.f(p.wstem), nullptr, nullptr, 0, ws.f(p.stem_raw), part, nz, B, C, h, w, stream));
-    RT_CALL(finalize(p, params, bn_state, part, p.stem_nblk, 64, (long long)B * p.Hs * p.Ws, p.stem_gb, p.stem_rs, sss, st));
+    RG_CALL(straps_stem_nzmask(x, nz, B, C, h, w, stream));
+    RG_CALL(straps_stem_fwd(x, ws.f(p.wstem), nullptr, nullptr, 0, ws.f(p.stem_raw), part, nz, B, C, h, w, stream));
+    RG_CALL(finalize(params, bn_state, part, p.stem_nblk, 64, (long long)B * p.geo.Hs * p.geo.Ws, p.stem.gb_off, p.stem.rs_off, sss, st));
     if (p.pool_planes)
-        RT_CALL(straps_bn_relu_maxpool_fwd_x3(ws.f(p.stem_raw), sss, sss + 64, ws.f(p.pool), (uint8_t*)(ws.base + p.idx), ws.h(p.pool3), p.pool_ps,
-                                              B, p.Hs, p.Ws, 64, stream));
+        RG_CALL(straps_bn_relu_maxpool_fwd_x3(ws.f(p.stem_raw), sss, sss + 64, ws.f(p.pool), (uint8_t*)(ws.base + p.idx), ws.h(p.pool3), p.pool_ps,
+                                              B, p.geo.Hs, p.geo.Ws, 64, stream));
     else
-        RT_CALL(straps_bn_relu_maxpool_fwd(ws.f(p.stem_raw), sss, sss + 64, ws.f(p.pool), (uint8_t*)(ws.base + p.idx), B, p.Hs, p.Ws, 64, stream));
+        RG_CALL(straps_bn_relu_maxpool_fwd(ws.f(p.stem_raw), sss, sss + 64, ws.f(p.pool), (uint8_t*)(ws.base + p.idx), B, p.geo.Hs, p.geo.Ws, 64, stream));
 
     // ---- residual stages (conv_bn in training mode with a tape) ----
-    auto conv_fwd = [&](const Conv& cv) -> int {
+    auto conv_fwd = [&](const Layer& cv) -> int {
         const float* sa = cv.a_bn ? ws.f(cv.a_bn->ss) : nullptr;
         if (cv.fmode)
             return straps_conv_fwd_x3f(ws.f(cv.x), sa, sa ? sa + cv.a_bn->cout : nullptr, cv.a_bn ? 1 : 0, krsc3 + cv.first, p.ps, nullptr, nullptr,
@@ -466,10 +344,10 @@ extern "C" int straps_regressor_fwd_train(const straps_regressor_desc_t* d, cons
         return straps_conv_fwd(ws.f(cv.x), krsc + cv.first, nullptr, nullptr, nullptr, 0, ws.f(cv.raw), part, B, cv.H, cv.W, cv.cin, cv.cout,
                                cv.k, cv.k, cv.stride, cv.pad, 0, stream);
     };
-    auto conv_bn = [&](const Conv& cv, const float* residual) -> int {
-        RT_CALL(conv_fwd(cv));
+    auto conv_bn = [&](const Layer& cv, const float* residual) -> int {
+        RG_CALL(conv_fwd(cv));
         float* ss = ws.f(cv.ss);
-        RT_CALL(finalize(p, params, bn_state, part, cv.nblk, cv.cout, cv.rows, cv.gb_off, cv.rs_off, ss, st));
+        RG_CALL(finalize(params, bn_state, part, cv.nblk, cv.cout, cv.rows, cv.gb_off, cv.rs_off, ss, st));
         if (cv.defer) return STRAPS_OK;
         if (x3 && cv.relu) {
             if (cv.bits)
@@ -481,33 +359,19 @@ extern "C" int straps_regressor_fwd_train(const straps_regressor_desc_t* d, cons
     };
     for (int ui = 0; ui < p.nunits; ++ui) {
         const Unit& u = p.units[ui];
-        const float* idt = ws.f(u.c[0].x);
+        const float* idt = ws.f(p.lay[u.c[0]].x);
         if (u.has_ds) {
-            RT_CALL(conv_bn(u.dsc, nullptr));
-            idt = ws.f(u.dsc.out);
+            RG_CALL(conv_bn(p.lay[u.ds], nullptr));
+            idt = ws.f(p.lay[u.ds].out);
         }
-        for (int ci = 0; ci < u.nconv; ++ci) RT_CALL(conv_bn(u.c[ci], u.c[ci].last ? idt : nullptr));
+        for (int ci = 0; ci < u.nconv; ++ci) RG_CALL(conv_bn(p.lay[u.c[ci]], p.lay[u.c[ci]].last ? idt : nullptr));
     }
 
-    // ---- global average pool, then the IEF iterations with every iteration's activations kept (IEFModule.forward_estimate) ----
-    const Conv& lastc = p.units[p.nunits - 1].c[p.units[p.nunits - 1].nconv - 1];
-    float* feat = ws.f(p.feat);
-    float* c1 = ws.f(p.c1);
-    float* ests = ws.f(p.ests);
-    RT_CALL(straps_gap_fwd(ws.f(lastc.out), feat, B, p.Hf * p.Wf, F, stream));
-    RT_CALL(straps_broadcast_rows(init_est, kNumParams, ests, kEstLd, (T + 1) * B, stream));
-    RT_CALL(straps_linear_fwd(feat, F, ws.f(p.w1f), F, params + p.fc1b, nullptr, c1, H1, B, H1, F, 0, stream));
-    const bool direct = ld_est == kEstLd;      // (the backward never reads the last slot: the last iteration may write `est` itself)
-    for (int it = 0; it < T; ++it) {
-        float* est_in = ests + (size_t)it * B * kEstLd;
-        float* est_out = direct && it == T - 1 ? est : est_in + (size_t)B * kEstLd;
-        float* h1 = ws.f(p.h1s) + (size_t)it * B * H1;
-        float* h2 = ws.f(p.h2s) + (size_t)it * B * H2;
-        RT_CALL(straps_linear_fwd(est_in, kEstLd, ws.f(p.w1e), kEstLd, nullptr, c1, h1, H1, B, H1, kEstLd, 1, stream));
-        RT_CALL(straps_linear_fwd(h1, H1, params + p.fc2w, H1, params + p.fc2b, nullptr, h2, H2, B, H2, H1, 1, stream));
-        RT_CALL(straps_linear_fwd(h2, H2, ws.f(p.w3), H2, params + p.fc3b, est_in, est_out, kEstLd, B, kNumParams, H2, 0, stream));
-    }
-    if (!direct) RT_CALL(straps_masked_copy(ests + (size_t)T * B * kEstLd, kEstLd, nullptr, 0, est, ld_est, B, kNumParams, 0, stream));
+    // ---- global average pool, then the IEF iterations with every iteration's activations kept (the backward never reads the last
+    // estimate slot: the last iteration may write `est` itself) ----
+    RG_CALL(ief_forward(p, B, ws.f(p.unit_out(p.nunits - 1).out), p.geo.Hf * p.geo.Wf, init_est, ws.f(p.w1f), ws.f(p.w1e), params + p.ief.fc1b,
+                        params + p.ief.fc2w, params + p.ief.fc2b, ws.f(p.w3), params + p.ief.fc3b, ws.f(p.feat), ws.f(p.c1), ws.f(p.ests),
+                        ws.f(p.h1s), (long long)B * H1, ws.f(p.h2s), (long long)B * H2, est, ld_est, stream));
     return STRAPS_OK;
 }
 
@@ -516,7 +380,7 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
                                     void* stream) {
     static const char* fn = "straps_regressor_bwd";
     Plan p;
-    RT_CALL(check_common(fn, d, params, x, batch, h, w, workspace, p));
+    RG_CALL(check_common(fn, d, params, x, batch, h, w, workspace, p));
     STRAPS_REQUIRE(dest, "%s: null pointer `dest`", fn);
     STRAPS_REQUIRE(ld_dest >= kNumParams, "%s: `ld_dest` must be >= %d (got %d)", fn, kNumParams, ld_dest);
     STRAPS_REQUIRE(((uintptr_t)dest & 3) == 0 && ((uintptr_t)grads & 3) == 0 && ((uintptr_t)dx & 3) == 0,
@@ -524,7 +388,6 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
     STRAPS_REQUIRE(!dx || p.cin <= STRAPS_STEM_DGRAD_MAX_CIN, "%s: `dx` needs `in_channels` <= %d (got %d)", fn, STRAPS_STEM_DGRAD_MAX_CIN, p.cin);
     STRAPS_REQUIRE(workspace_bytes >= p.bytes, "%s: `workspace_bytes` is %zu, this batch needs %zu (straps_regressor_train_workspace_bytes)", fn,
                    workspace_bytes, p.bytes);
-    hipStream_t st = (hipStream_t)stream;
     const Ws ws{(char*)workspace};
     const int B = batch, C = p.cin, F = p.F, H1 = p.H1, H2 = p.H2, T = p.iters, P = kNumParams;
     const bool x3 = p.x3, pg = grads != nullptr;
@@ -543,7 +406,7 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
     const float* ests = ws.f(p.ests);
     const float* h1s = ws.f(p.h1s);
     const float* h2s = ws.f(p.h2s);
-    RT_CALL(straps_masked_copy(dest, ld_dest, nullptr, 0, dests + (size_t)T * B * kEstLd, kEstLd, B, P, 0, stream));
+    RG_CALL(straps_masked_copy(dest, ld_dest, nullptr, 0, dests + (size_t)T * B * kEstLd, kEstLd, B, P, 0, stream));
     auto gd = [](const float* a, long long sam, long long sak, const float* b, long long sbk, long long sbn, float* c, int ldc, int m, int n, int k) {
         straps_gemm_desc_t g;
         memset(&g, 0, sizeof(g));
@@ -554,33 +417,33 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
         float* dnext = dests + (size_t)(it + 1) * B * kEstLd;
         float* dh2 = dh2s + (size_t)it * B * H2;
         float* dh1 = dh1s + (size_t)it * B * H1;
-        straps_gemm_desc_t g = gd(dnext, kEstLd, 1, params + p.fc3w, H2, 1, dh2, H2, B, H2, P);
+        straps_gemm_desc_t g = gd(dnext, kEstLd, 1, params + p.ief.fc3w, H2, 1, dh2, H2, B, H2, P);
         g.mask = h2s + (size_t)it * B * H2; g.ldmask = H2;
-        RT_CALL(straps_gemm_multi(&g, 1, stream));
-        g = gd(dh2, H2, 1, params + p.fc2w, H1, 1, dh1, H1, B, H1, H2);
+        RG_CALL(straps_gemm_multi(&g, 1, stream));
+        g = gd(dh2, H2, 1, params + p.ief.fc2w, H1, 1, dh1, H1, B, H1, H2);
         g.mask = h1s + (size_t)it * B * H1; g.ldmask = H1;
         g.c2 = dc1; g.ldc2 = H1; g.accumulate2 = it != T - 1;
-        RT_CALL(straps_gemm_multi(&g, 1, stream));
+        RG_CALL(straps_gemm_multi(&g, 1, stream));
         g = gd(dh1, H1, 1, ws.f(p.w1e), kEstLd, 1, dests + (size_t)it * B * kEstLd, kEstLd, B, P, H1);
         g.addend = dnext; g.ldadd = kEstLd;
-        RT_CALL(straps_gemm_multi(&g, 1, stream));
+        RG_CALL(straps_gemm_multi(&g, 1, stream));
     }
     if (!pg) {
         const straps_gemm_desc_t g = gd(dc1, H1, 1, ws.f(p.w1f), F, 1, dfeat, F, B, F, H1);
-        RT_CALL(straps_gemm_multi(&g, 1, stream));
+        RG_CALL(straps_gemm_multi(&g, 1, stream));
     } else {
         const int KB = T * B;
         const float* one = ws.f(p.one);
         const straps_gemm_desc_t g[8] = {
-            gd(dh2s, 1, H2, h1s, H1, 1, grads + p.fc2w, H1, H2, H1, KB),
-            gd(dc1, 1, H1, ws.f(p.feat), F, 1, grads + p.fc1w, F + P, H1, F, B),
-            gd(dh1s, 1, H1, ests, kEstLd, 1, grads + p.fc1w + F, F + P, H1, P, KB),
-            gd(dests + (size_t)B * kEstLd, 1, kEstLd, h2s, H2, 1, grads + p.fc3w, H2, P, H2, KB),
+            gd(dh2s, 1, H2, h1s, H1, 1, grads + p.ief.fc2w, H1, H2, H1, KB),
+            gd(dc1, 1, H1, ws.f(p.feat), F, 1, grads + p.ief.fc1w, F + P, H1, F, B),
+            gd(dh1s, 1, H1, ests, kEstLd, 1, grads + p.ief.fc1w + F, F + P, H1, P, KB),
+            gd(dests + (size_t)B * kEstLd, 1, kEstLd, h2s, H2, 1, grads + p.ief.fc3w, H2, P, H2, KB),
             gd(dc1, H1, 1, ws.f(p.w1f), F, 1, dfeat, F, B, F, H1),
-            gd(one, 0, 0, dh2s, H2, 1, grads + p.fc2b, H2, 1, H2, KB),
-            gd(one, 0, 0, dests + (size_t)B * kEstLd, kEstLd, 1, grads + p.fc3b, P, 1, P, KB),
-            gd(one, 0, 0, dc1, H1, 1, grads + p.fc1b, H1, 1, H1, B)};
-        RT_CALL(straps_gemm_multi(g, 8, stream));
+            gd(one, 0, 0, dh2s, H2, 1, grads + p.ief.fc2b, H2, 1, H2, KB),
+            gd(one, 0, 0, dests + (size_t)B * kEstLd, kEstLd, 1, grads + p.ief.fc3b, P, 1, P, KB),
+            gd(one, 0, 0, dc1, H1, 1, grads + p.ief.fc1b, H1, 1, H1, B)};
+        RG_CALL(straps_gemm_multi(g, 8, stream));
     }
 
     // ---- encoder (autograd_ops.encoder_backward, one stream) ----
@@ -589,13 +452,13 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
     double* part = (double*)(ws.base + p.part);
     void* bnws = ws.base + p.bnws;
     void* wgws = ws.base + p.wgws;
-    const Conv* pending = nullptr;     // the BatchNorm whose backward sums the last data gradient accumulated (rec['bwd_partials'])
+    const Layer* pending = nullptr;     // the BatchNorm whose backward sums the last data gradient accumulated (rec['bwd_partials'])
     int pending_nblk = 0;
     int cur = 0;
-    RT_CALL(straps_gap_bwd(dfeat, ws.f(p.g[cur]), B, p.Hf * p.Wf, F, stream));
+    RG_CALL(straps_gap_bwd(dfeat, ws.f(p.g[cur]), B, p.geo.Hf * p.geo.Wf, F, stream));
 
     // BatchNorm (+ ReLU) backward of one layer (_bn_bwd); out_off / out3_off: the slots of draw and its planes
-    auto bn_bwd = [&](const Conv& cv, const float* dy, bool masked, float* dz, const unsigned* mask_bits, size_t out_off, size_t out3_off) -> int {
+    auto bn_bwd = [&](const Layer& cv, const float* dy, bool masked, float* dz, const unsigned* mask_bits, size_t out_off, size_t out3_off) -> int {
         const float* ss = ws.f(cv.ss);
         const int c = cv.cout;
         const bool sink = x3 && !cv.fmode;
@@ -623,7 +486,7 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
                                 from_raw ? ss : nullptr, from_raw ? ss + c : nullptr, dg, db, draw, dz, planes, ps, bnws, cv.rows, c, 0, stream);
     };
     // weight gradient of one layer (_conv_wgrad); draw_off / draw3_off: its output gradient
-    auto wgrad = [&](const Conv& cv, size_t draw_off, size_t draw3_off) -> int {
+    auto wgrad = [&](const Layer& cv, size_t draw_off, size_t draw3_off) -> int {
         if (!pg) return STRAPS_OK;
         float* dw = grads + cv.w_off;
         if (cv.fmode) {
@@ -637,7 +500,7 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
         return straps_conv_wgrad(ws.f(cv.x), ws.f(draw_off), dw, wgws, B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0, stream);
     };
     // data gradient of one layer (_conv_dgrad); bn_next: the BatchNorm whose output it read (bf16x3: its backward sums ride along)
-    auto dgrad = [&](const Conv& cv, size_t draw_off, size_t draw3_off, const float* addend, const unsigned* addend_bits, const Conv* bn_next,
+    auto dgrad = [&](const Layer& cv, size_t draw_off, size_t draw3_off, const float* addend, const unsigned* addend_bits, const Layer* bn_next,
                      float* out) -> int {
         const long long gps = round8(cv.rows * cv.cout);
         if (cv.fmode) {
@@ -657,7 +520,7 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
                     if (from_raw) { msc = ssn; msh = ssn + cn; }
                 }
             }
-            RT_CALL(straps_conv_dgrad_x3f(ws.f(draw_off), crsk3 + cv.first, p.ps, addend, addend_bits, out, B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k,
+            RG_CALL(straps_conv_dgrad_x3f(ws.f(draw_off), crsk3 + cv.first, p.ps, addend, addend_bits, out, B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k,
                                           cv.stride, cv.pad, 0, raw, nbits, msc, msh, mean, invstd, prt, stream));
             if (prt) { pending = bn_next; pending_nblk = nblk; }
             return STRAPS_OK;
@@ -672,12 +535,12 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
                 const int nblk = straps_conv_dgrad_x3_bn_blocks(B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0);
                 const unsigned* nbits = from_raw ? nullptr : ws.u(bn_next->bitsb);
                 if (addend_bits || nbits)
-                    RT_CALL(straps_conv_dgrad_x3_bn_bits(g3, gps, w3, p.ps, addend, out, B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0,
+                    RG_CALL(straps_conv_dgrad_x3_bn_bits(g3, gps, w3, p.ps, addend, out, B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0,
                                                          ws.f(bn_next->raw), (from_raw || nbits) ? nullptr : ws.f(bn_next->out),
                                                          from_raw ? ssn : nullptr, from_raw ? ssn + cn : nullptr, ssn + 2 * cn, ssn + 3 * cn, part,
                                                          addend_bits, nbits, stream));
                 else
-                    RT_CALL(straps_conv_dgrad_x3_bn(g3, gps, w3, p.ps, addend, out, B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0,
+                    RG_CALL(straps_conv_dgrad_x3_bn(g3, gps, w3, p.ps, addend, out, B, cv.H, cv.W, cv.cin, cv.cout, cv.k, cv.k, cv.stride, cv.pad, 0,
                                                     ws.f(bn_next->raw), from_raw ? nullptr : ws.f(bn_next->out), from_raw ? ssn : nullptr,
                                                     from_raw ? ssn + cn : nullptr, ssn + 2 * cn, ssn + 3 * cn, part, stream));
                 pending = bn_next;
@@ -693,35 +556,36 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
     };
     for (int ui = p.nunits - 1; ui >= 0; --ui) {
         const Unit& u = p.units[ui];
-        const Conv* prev_last = ui > 0 ? &p.units[ui - 1].c[p.units[ui - 1].nconv - 1] : nullptr;
-        const Conv& lc = u.c[u.nconv - 1];
+        const Layer* prev_last = ui > 0 ? &p.unit_out(ui - 1) : nullptr;
+        const Layer& lc = p.unit_out(ui);
         const float* dy = ws.f(p.g[cur]);
         const unsigned* ubits = x3 ? ws.u(lc.bitsb) : nullptr;
         const float* dz = dy;
         if (ubits) {
-            RT_CALL(bn_bwd(lc, dy, true, nullptr, nullptr, p.draw, p.draw3));
+            RG_CALL(bn_bwd(lc, dy, true, nullptr, nullptr, p.draw, p.draw3));
         } else {
-            RT_CALL(bn_bwd(lc, dy, true, ws.f(p.dz), nullptr, p.draw, p.draw3));
+            RG_CALL(bn_bwd(lc, dy, true, ws.f(p.dz), nullptr, p.draw, p.draw3));
             dz = ws.f(p.dz);
         }
-        RT_CALL(wgrad(lc, p.draw, p.draw3));
+        RG_CALL(wgrad(lc, p.draw, p.draw3));
         const float* dskip = dz;
         const unsigned* dskip_bits = nullptr;
         if (u.has_ds) {
-            RT_CALL(bn_bwd(u.dsc, dz, false, nullptr, ubits, p.drawd, p.drawd3));
-            RT_CALL(wgrad(u.dsc, p.drawd, p.drawd3));
-            RT_CALL(dgrad(u.dsc, p.drawd, p.drawd3, nullptr, nullptr, nullptr, ws.f(p.dskip)));
+            const Layer& ds = p.lay[u.ds];
+            RG_CALL(bn_bwd(ds, dz, false, nullptr, ubits, p.drawd, p.drawd3));
+            RG_CALL(wgrad(ds, p.drawd, p.drawd3));
+            RG_CALL(dgrad(ds, p.drawd, p.drawd3, nullptr, nullptr, nullptr, ws.f(p.dskip)));
             dskip = ws.f(p.dskip);
         } else {
             dskip_bits = ubits;
         }
         for (int ci = u.nconv - 1; ci > 0; --ci) {
-            const Conv& prev = u.c[ci - 1];
-            RT_CALL(dgrad(u.c[ci], p.draw, p.draw3, nullptr, nullptr, x3 ? &prev : nullptr, ws.f(p.dt)));
-            RT_CALL(bn_bwd(prev, ws.f(p.dt), true, nullptr, nullptr, p.draw, p.draw3));
-            RT_CALL(wgrad(prev, p.draw, p.draw3));
+            const Layer& prev = p.lay[u.c[ci - 1]];
+            RG_CALL(dgrad(p.lay[u.c[ci]], p.draw, p.draw3, nullptr, nullptr, x3 ? &prev : nullptr, ws.f(p.dt)));
+            RG_CALL(bn_bwd(prev, ws.f(p.dt), true, nullptr, nullptr, p.draw, p.draw3));
+            RG_CALL(wgrad(prev, p.draw, p.draw3));
         }
-        RT_CALL(dgrad(u.c[0], p.draw, p.draw3, dskip, dskip_bits, x3 ? prev_last : nullptr, ws.f(p.g[cur ^ 1])));
+        RG_CALL(dgrad(p.lay[u.c[0]], p.draw, p.draw3, dskip, dskip_bits, x3 ? prev_last : nullptr, ws.f(p.g[cur ^ 1])));
         cur ^= 1;
     }
 
@@ -731,33 +595,33 @@ extern "C" int straps_regressor_bwd(const straps_regressor_desc_t* d, const floa
     uint8_t* tact = nullptr;
     if (!dx) {      // the weight gradient -- draw's only reader -- skips the tiles without a non-zero input under them
         tact = (uint8_t*)(ws.base + p.tact);
-        RT_CALL(straps_stem_tile_activity(nz, tact, B, C, h, w, stream));
+        RG_CALL(straps_stem_tile_activity(nz, tact, B, C, h, w, stream));
     }
     float* sdraw = ws.f(p.sdraw);
-    RT_CALL(straps_bn_bwd_pooled_sparse(ws.f(p.g[cur]), (const uint8_t*)(ws.base + p.idx), ws.f(p.stem_raw), sss + 128, sss + 192, params + p.stem_gb,
-                                        sss, sss + 64, dgamma(p.stem_gb), dbeta(p.stem_gb, 64), sdraw, bnws, B, p.Hs, p.Ws, 64, 0, tact, stream));
+    RG_CALL(straps_bn_bwd_pooled_sparse(ws.f(p.g[cur]), (const uint8_t*)(ws.base + p.idx), ws.f(p.stem_raw), sss + 128, sss + 192, params + p.stem.gb_off,
+                                        sss, sss + 64, dgamma(p.stem.gb_off), dbeta(p.stem.gb_off, 64), sdraw, bnws, B, p.geo.Hs, p.geo.Ws, 64, 0, tact, stream));
     if (dx) {
-        RT_CALL(straps_pack_stem_dgrad_weight(params + p.stem_w, ws.f(p.wsd), C, stream));
-        RT_CALL(straps_stem_dgrad(sdraw, ws.f(p.wsd), dx, B, C, h, w, 0, stream));
+        RG_CALL(straps_pack_stem_dgrad_weight(params + p.stem.w_off, ws.f(p.wsd), C, stream));
+        RG_CALL(straps_stem_dgrad(sdraw, ws.f(p.wsd), dx, B, C, h, w, 0, stream));
     }
-    if (pg) RT_CALL(straps_stem_wgrad(x, sdraw, grads + p.stem_w, ws.base + p.swgws, nz, B, C, h, w, 0, stream));
+    if (pg) RG_CALL(straps_stem_wgrad(x, sdraw, grads + p.stem.w_off, ws.base + p.swgws, nz, B, C, h, w, 0, stream));
     return STRAPS_OK;
 }
 
 extern "C" int straps_regressor_export_infer_params(const straps_regressor_desc_t* d, const float* params, const float* bn_state,
                                                     const float* init_est, float* infer_params, void* stream) {
     static const char* fn = "straps_regressor_export_infer_params";
-    const char* bad = check_desc(d);
+    const char* bad = check_desc(d, true);
     STRAPS_REQUIRE(!bad, "%s: %s", fn, bad);
     STRAPS_REQUIRE(params, "%s: null pointer `params`", fn);
     STRAPS_REQUIRE(bn_state, "%s: null pointer `bn_state`", fn);
     STRAPS_REQUIRE(init_est, "%s: null pointer `init_est`", fn);
     STRAPS_REQUIRE(infer_params, "%s: null pointer `infer_params`", fn);
-    Plan p;
-    make_layout(d, p);
+    Net n;
+    make_net(d, n);
     hipStream_t st = (hipStream_t)stream;
-    auto copy = [&](long long dst, const float* src, long long n) -> int {
-        const hipError_t e = hipMemcpyAsync(infer_params + dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    auto copy = [&](long long dst, const float* src, long long count) -> int {
+        const hipError_t e = hipMemcpyAsync(infer_params + dst, src, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) {
             straps_set_error("%s: hipMemcpyAsync failed: %s", fn, hipGetErrorString(e));
             return STRAPS_EHIP;
@@ -765,16 +629,14 @@ extern "C" int straps_regressor_export_infer_params(const straps_regressor_desc_
         return STRAPS_OK;
     };
     // per layer: weight, gamma + beta (adjacent in `params`), running mean + var (adjacent in `bn_state`)
-    RT_CALL(copy(p.inf_stem_w, params + p.stem_w, 64LL * p.cin * 49));
-    RT_CALL(copy(p.inf_stem_bn, params + p.stem_gb, 128));
-    RT_CALL(copy(p.inf_stem_bn + 128, bn_state + p.stem_rs, 128));
-    for (int i = 0; i < p.nconvs; ++i) {
-        const Conv& cv = *p.convs[i];
-        RT_CALL(copy(cv.inf_w, params + cv.w_off, (long long)cv.cout * cv.cin * cv.k * cv.k));
-        RT_CALL(copy(cv.inf_bn, params + cv.gb_off, 2LL * cv.cout));
-        RT_CALL(copy(cv.inf_bn + 2LL * cv.cout, bn_state + cv.rs_off, 2LL * cv.cout));
-    }
-    RT_CALL(copy(p.inf_fc1w, params + p.fc1w, p.param_floats - p.fc1w));      // the IEF tensors: the same order in both layouts
-    RT_CALL(copy(p.inf_init, init_est, kNumParams));
+    auto layer = [&](const Conv& cv) -> int {
+        RG_CALL(copy(cv.inf_w, params + cv.w_off, cv.weights()));
+        RG_CALL(copy(cv.inf_bn, params + cv.gb_off, 2LL * cv.cout));
+        return copy(cv.inf_bn + 2LL * cv.cout, bn_state + cv.rs_off, 2LL * cv.cout);
+    };
+    RG_CALL(layer(n.stem));
+    for (int i = 0; i < n.nconvs; ++i) RG_CALL(layer(n.convs[i]));
+    RG_CALL(copy(n.ief_inf.fc1w, params + n.ief.fc1w, n.train_floats - n.ief.fc1w));      // the IEF tensors: the same order in both layouts
+    RG_CALL(copy(n.inf_init, init_est, kNumParams));
     return STRAPS_OK;
 }
