@@ -331,7 +331,12 @@ int straps_smpl_fwd(const straps_smpl_model_t* model, const float* betas, const 
 
 /* gradient of straps_smpl_fwd w.r.t. betas [B,10] and rotmats [B,24,3,3] given dverts [B,6890,3]
  * and/or djoints [B,90,3] (either may be NULL = zero) -- what autograd does through smplx.lbs for
- * pred_smpl_output in loss.backward() (train loop :196,:232).                                    */
+ * pred_smpl_output in loss.backward() (train loop :196,:232).
+ * chunks: split of the 54 rounds of 4 vertex tiles over workgroups; 0 (or negative) = 8 from 1024 bodies on, 54 below; values above
+ * 54 are 54.  A chunk takes ceil(54 / chunks) rounds, so used = ceil(54 / ceil(54 / chunks)) chunks run (5 -> 5 chunks of 11, 11, 11,
+ * 11, 10 rounds; 20 -> 18 chunks of 3).  Workspace: batch * (1 + used) * (224 + 288) * 4 bytes -- the recomputed pose features and joint
+ * transforms of every body, and one partial of their gradients per chunk.  Results for different `chunks` differ by summation order
+ * only; for one value they are bit-reproducible and a body's result does not depend on the rest of the batch.                    */
 size_t straps_smpl_bwd_workspace_bytes(long long batch, int chunks);
 int straps_smpl_bwd(const straps_smpl_model_t* model, const float* betas, const float* rotmats,
                     const float* dverts, const float* djoints, float* dbetas, float* drotmats,

@@ -379,7 +379,7 @@ extern "C" int straps_loss_fwd_bwd_gm(const float* pred_verts, const float* pred
                        log_vars && loss_out && workspace,
                    "straps_loss_fwd_bwd: null pointer");
     STRAPS_REQUIRE(batch > 0 && ld_est >= 157, "straps_loss_fwd_bwd: bad shape batch=%lld ld_est=%d", batch, ld_est);
-    const bool want_grad = dverts || djoints || dest || drot;
+    const bool want_grad = dverts || djoints || dest || drot || dlogvar;      // (dlogvar alone used to pass as the loss-only form)
     STRAPS_REQUIRE(!want_grad || (dverts && djoints && dest && drot && dlogvar), "straps_loss_fwd_bwd: give all gradient outputs or none");
     hipStream_t st = (hipStream_t)stream;
     float* vpart = (float*)workspace;

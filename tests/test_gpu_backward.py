@@ -18,6 +18,7 @@ import straps_amd
 import straps_oracle as O
 import decisions
 from detgen import det_uniform, det_state_dict
+from loss_cases import oracle_loss
 from straps_amd import hipabi
 
 pytestmark = pytest.mark.gpu
@@ -660,15 +661,9 @@ def test_fused_loss_vs_oracle(dev):
     trot = torch.from_numpy(det_uniform((B, 24, 3, 3), 68))
     lv0 = O.init_log_vars({'verts': 1.0, 'joints2D': 0.1, 'pose_params': 0.1, 'shape_params': 0.1, 'joints3D': 1.0})
     order = ('verts', 'joints2D', 'joints3D', 'shape_params', 'pose_params')
-    # oracle with autograd
-    J, E, PR, PV = joints.double().requires_grad_(), est.double().requires_grad_(), prot.double().requires_grad_(), pverts.double().requires_grad_()
-    lv = {k: torch.tensor(lv0[k], dtype=torch.float64, requires_grad=True) for k in order}
-    outp = {'verts': PV, 'joints2D': O.orthographic_project(J[:, O.ALL_JOINTS_TO_COCO_MAP], E[:, :3]),
-            'joints3D': J[:, O.ALL_JOINTS_TO_H36M_MAP][:, O.H36M_TO_J14], 'shape_params': E[:, 147:157], 'pose_params_rot_matrices': PR}
-    lab = {'verts': tverts.double(), 'joints2D': tj2d.double(), 'joints3D': tj3d.double(), 'shape_params': tshape.double(),
-           'pose_params_rot_matrices': trot.double(), 'vis': O.check_joints2d_visibility(tj2d)}
-    total, parts = O.multi_task_loss(lab, outp, lv)
-    total.backward()
+    # oracle with autograd (the composition shared with tests/test_gpu_loss_head_edges.py)
+    total, parts, lab, leaf, lv = oracle_loss(joints, est, prot, pverts, tverts, tj2d, tj3d, tshape, trot, lv0)
+    J, E, PR, PV = leaf['J'], leaf['E'], leaf['PR'], leaf['PV']
     d = lambda t: t.to(dev).contiguous()
     tens = [d(pverts), d(joints), d(est), d(prot), d(tverts), d(tj2d), d(tj3d), d(tshape), d(trot)]
     lvd = torch.tensor([lv0[k] for k in order], dtype=torch.float32, device=dev)

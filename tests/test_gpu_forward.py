@@ -17,6 +17,7 @@ import torch.nn.functional as F
 import straps_amd
 import straps_oracle as O
 from detgen import det_uniform, det_state_dict
+from smpl_cases import real_magnitude_model
 from straps_amd import hipabi
 
 pytestmark = pytest.mark.gpu
@@ -128,14 +129,8 @@ def test_smpl_pd16_mode_vs_oracle(dev, smpl_model, B, mode):
         assert torch.equal(vs, v[30:37]) and torch.equal(js, j[30:37])
 
 
-def _real_magnitude_model(model):
-    """the synthetic SMPL model with its blend directions scaled to the real model's magnitudes (missing #3): the synthetic
-    posedirs are uniform +-1e-3 where SMPL_NEUTRAL's largest entries are one to two orders larger, and the shape directions about three times
-    smaller than the real ones -- every 'm from float64' figure of the split-precision modes above is a statement about the SMALL directions."""
-    big = dict(model)
-    big['posedirs'] = (np.asarray(model['posedirs'], dtype=np.float64) * 50.0).astype(np.float32)
-    big['shapedirs'] = (np.asarray(model['shapedirs'], dtype=np.float64) * 3.0).astype(np.float32)
-    return big
+# (the synthetic model at the real model's direction magnitudes: shared with the SMPL-gradient edge tests)
+_real_magnitude_model = real_magnitude_model
 
 
 # mode -> bar in metres at the real model's magnitudes.  The three parity-grade modes keep the 2e-5 of every SMPL test here (north_star: 1e-4).
