@@ -15,8 +15,6 @@
 //   3. smpl_joints_kernel : picked vertices + the 45 sparse-regressed joints, gathered from the
 //                           just-written vertices in a fixed order.
 // Everything is deterministic (no atomics).
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace {
@@ -310,11 +308,11 @@ constexpr float F_SCALE = 64.0f;          // 2^6
 
 __device__ __forceinline__ f32x16 mfma16h(half8 a, half8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
-template <int PF>
 __global__ __launch_bounds__(NW * 64) STRAPS_NO_PACKED_FP32 void smpl_verts_h_kernel(straps_smpl_model_t m, const float* __restrict__ F,
                                                                const float* __restrict__ Amat, float* __restrict__ verts,
                                                                float* __restrict__ vout, long long B, int btiles,
                                                                int rounds, int rounds_per_chunk) {
+    constexpr int PF = 3;                  // k-steps the fragment loads run ahead of the MFMAs
     extern __shared__ __attribute__((aligned(16))) float smem[];
     _Float16* Fh = reinterpret_cast<_Float16*>(smem);            // [32][FSH] high halves of the scaled features
     _Float16* Fl = Fh + BT * FSH;                                  // [32][FSH] low halves
@@ -511,8 +509,8 @@ constexpr float W_UNSCALE = 1.0f / (16384.0f * 1024.0f);   // weights are scaled
 // bytes from L2 (the fragment stream, 19 MB per 32 bodies, is what bounds this kernel).  Template + shape (+ the first five pose
 // features, k step 0) keep the three-product split.  Error: ~2^-12 of the pose-corrective sum -- measured in the tests.
 // PD16 = 2 (mode STRAPS_SMPL_SPLIT_F16_LBS_P16): additionally the pose FEATURES of those columns as plain fp16 -- one product.
-template <int NWV, int PF, int ABL, int PD16 = 0>
-__global__ __launch_bounds__(NWV * 64) void smpl_verts_hh_kernel(straps_smpl_model_t m, const float* __restrict__ F,
+template <int PD16>
+__global__ __launch_bounds__(NW * 64) void smpl_verts_hh_kernel(straps_smpl_model_t m, const float* __restrict__ F,
                                                                  const float* __restrict__ Amat, float* __restrict__ verts,
                                                                  float* __restrict__ vout, long long B, int btiles,
                                                                  int ntiles, int rounds, int rounds_per_chunk, unsigned long long* clk) {
@@ -520,9 +518,9 @@ __global__ __launch_bounds__(NWV * 64) void smpl_verts_hh_kernel(straps_smpl_mod
     //  its lifetime, bench.py's sclk_mhz of the SMPL-only workload)
     unsigned long long clk_c0 = 0, clk_w0 = 0;
     if (clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_w0 = __builtin_amdgcn_s_memrealtime(); }
-    // (ABL: compile-time measurement switches, 0 in production -- 1 = no output stores, 2 = no fragment loads after the first
-    //  k-step, 4 = no skinning MFMAs, 8 = no blend MFMAs; tools/smpl_ablate.sh)
-    constexpr int ablate = ABL;
+    // (8 waves: 12 / 16 per workgroup need <= 168 / 128 VGPRs -- the kernel spills and runs 3.5x slower.  A ring deeper than PF = 2 does not
+    //  fit: it uses 255 of the 256 registers two waves per SIMD leave a wave)
+    constexpr int NWV = NW, PF = 2;
     // OPERAND ROLES ARE SWAPPED with respect to the two kernels above: the per-body operand (features, joint transforms) is the
     // MFMA's A side (i = body) and the per-vertex operand (blend directions, skinning weights) its B side (n = vertex), so the
     // accumulators hold lane = VERTEX, register = body row.  A lane's x,y,z of one (body, vertex) are then 12 contiguous bytes
@@ -645,7 +643,6 @@ __global__ __launch_bounds__(NWV * 64) void smpl_verts_hh_kernel(straps_smpl_mod
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int body = (r & 3) + 8 * (r >> 2) + 4 * h;
-            if ((ablate & 1) && o3[0][r] != 12345.678f) continue;          // (never true: keeps the arithmetic alive)
             if (vok && body < nb) {
                 float* o = vbase + body * rstride;
                 o[0] = o3[0][r]; o[1] = o3[1][r]; o[2] = o3[2][r];
@@ -669,7 +666,7 @@ __global__ __launch_bounds__(NWV * 64) void smpl_verts_hh_kernel(straps_smpl_mod
             const half8* p = blend + (long long)tile * (KS * 6 * 64) + lane;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                if (s + PF < KS && !(ablate & 2)) {
+                if (s + PF < KS) {
                     const half8* q = p + (s + PF) * 384;
 #pragma unroll
                     for (int f = 0; f < 6; ++f)
@@ -682,11 +679,9 @@ __global__ __launch_bounds__(NWV * 64) void smpl_verts_hh_kernel(straps_smpl_mod
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 const half8* c = ring[s % (PF + 1)];
-                if (!(ablate & 8)) {
                 ax = mfma16h(fh, c[0], ax); ay = mfma16h(fh, c[2], ay); az = mfma16h(fh, c[4], az);       // Fh . Dh
                 if (!(PD16 && s >= 1)) { ax = mfma16h(fh, c[1], ax); ay = mfma16h(fh, c[3], ay); az = mfma16h(fh, c[5], az); }       // Fh . Dl
                 if (!(PD16 == 2 && s >= 1)) { ax = mfma16h(fl, c[0], ax); ay = mfma16h(fl, c[2], ay); az = mfma16h(fl, c[4], az); }       // Fl . Dh
-                } else { ax[0] += (float)fh[0] + (float)c[0][0]; ay[0] += (float)fl[1] + (float)c[3][1]; az[0] += (float)c[5][2]; }
                 fh = fhn; fl = fln;
             }
             // the head of the NEXT tile's fragments is issued before this tile's stores: a load issued behind stores can only be
@@ -722,14 +717,12 @@ __global__ __launch_bounds__(NWV * 64) void smpl_verts_hh_kernel(straps_smpl_mod
             }
             __builtin_amdgcn_sched_barrier(0);
             f32x16 T = zero16;
-            if (e < 12 && !(ablate & 4)) {
+            if (e < 12) {
                 T = mfma16h(a0, sw0, zero16);
                 T = mfma16h(a1, sw1, T);
                 T = mfma16h(a2, sw2, T);
                 T = mfma16h(a0, sw3, T);                      // (packed k-steps 3, 4: the operands of 0, 1 again)
                 T = mfma16h(a1, sw4, T);
-            } else if (e < 12) {
-                T[0] = (float)a0[0] + (float)a2[1];
             }
             if (e > 0) {                                  // fold entry e-1 (Tprev) while the chain above is in the pipe
                 const int pe = e - 1, c = pe >> 2, q = pe & 3;
@@ -781,16 +774,14 @@ __global__ __launch_bounds__(NWV * 64) void smpl_verts_hh_kernel(straps_smpl_mod
 //   * joint transforms are staged as packed [Ah 24 | Al 24 | pad 8] rows of 112 bytes (conflict-free b128 reads), 84 KB for 64 bodies next
 //     to the 58 KB of split features: 142 KB of the 160 KB, one workgroup per CU.
 // Same arithmetic class as the kernel above (every product split three ways, fp32 accumulate); the skinning products are added in one
-// K-packed chain, so results may differ from it in the last bit.  Operand roles, output mapping and the store form are unchanged.
+// K-packed chain, so results may differ from it in the last bit.  Operand roles and output mapping are unchanged; the stores leave as
+// non-temporal buffer stores spread over the next tile's blend phase (store_one below).
 constexpr int WB = 64;                    // bodies per workgroup
 constexpr int NWW = 4;                    // waves per workgroup = one per SIMD
 
 // v_mfma_f32_32x32x16_f16 with VGPR C / D.  The hazard recogniser does not see inside inline assembly; the two rules this kernel relies on
 // (MI355X guide, "inline assembly"; the compiler's own code for the builtin shows the same): an accumulate chain (D of one = C of the next,
 // whole) needs no wait states; any other reader of D needs 11 (8-pass instruction) -- provided by construction, see the skinning loop.
-__device__ __forceinline__ void mfma16h_v0(f32x16& d, const half8& a, const half8& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
-}
 __device__ __forceinline__ void mfma16h_v(f32x16& d, const half8& a, const half8& b) {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
@@ -800,17 +791,13 @@ __device__ __forceinline__ void mfma16h_v01(f32x16& d, const half8& a0, const ha
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0\n\tv_mfma_f32_32x32x16_f16 %0, %3, %4, %0" : "=&v"(d) : "v"(a0), "v"(b0), "v"(a1), "v"(b1));
 }
 
-// ABL (tools build only; wrong results by design -- tools/smpl_w_ab.py --ablate): 1 = no output stores, 2 = no fragment loads after the
-// prologue, 4 = no skinning MFMA chains, 8 = no blend MFMAs, 16 = no fold on the VALU, 32 = no LDS operand reads inside the tile loop
-// SV: store / schedule variant bits -- 1 = non-temporal stores (the 5.5 GB of output stream through L2 without displacing the direction
-// fragments the 32 CUs of an XCD share), 2 = the four waves of a workgroup start a quarter of a tile period apart (the chip's store bursts
-// spread in time), 4 = the stores of tile t are issued inside the blend phase of tile t + 1, right after its last in-tile load request
-template <int PF, int PD16, int TV, int ABL = 0, int SV = 0>
+// TV = 0 is the builtin-MFMA reference form of the skinning chains (STRAPS_SMPL_KERNEL_WIDE_BUILTIN), TV = 1 the product.
+template <int PD16, int TV>
 __global__ __launch_bounds__(NWW * 64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, const float* __restrict__ Amat, float* __restrict__ verts,
                          float* __restrict__ vout, long long B, int bgroups, int ntiles, int rounds, int rounds_per_chunk,
                          unsigned long long* clk) {
-    static_assert(PF >= 1 && PF < KS, "prefetch distance");
+    constexpr int PF = 3;                  // k-steps the fragment requests run ahead of the MFMAs (profiles/r04_smpl_w_ab.txt)
     constexpr int R = PF + 1;              // ring slots
     unsigned long long clk_c0 = 0, clk_w0 = 0;
     if (clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_w0 = __builtin_amdgcn_s_memrealtime(); }
@@ -906,63 +893,43 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
         for (int f = 0; f < 6; ++f)
             if (!(PD16 && ks >= 1 && (f & 1))) slot[f] = q[f * 64];
     };
-    // one 12-byte-per-lane store: row r of group g's result tile t.  SV >> 8 selects the form: 0 = plain global store, 1 = non-temporal global
-    // store, 100 + aux = buffer store with that cache policy (gfx940 aux bits: 1 = sc0, 2 = nt, 16 = sc1)
-    constexpr int SP = SV >> 8;
-    typedef float f32x3 __attribute__((ext_vector_type(3)));
+    // one 12-byte-per-lane store: row r of group g's result tile t, as a non-temporal buffer store (gfx940 aux bit 2 = nt: the 5.5 GB of
+    // output stream through L2 without displacing the direction fragments the 32 CUs of an XCD share)
+    constexpr int AUX_NT = 2;
     typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-    __amdgpu_buffer_rsrc_t rs_mesh, rs_virt;
-    if (SP >= 100) {
-        rs_mesh = __builtin_amdgcn_make_buffer_rsrc(verts + b0 * (long long)(NV * 3), 0, 0x7fffffff, 0x00020000);
-        rs_virt = __builtin_amdgcn_make_buffer_rsrc((vout ? vout : verts) + b0 * (long long)vrow_floats, 0, 0x7fffffff, 0x00020000);
-    }
+    const __amdgpu_buffer_rsrc_t rs_mesh = __builtin_amdgcn_make_buffer_rsrc(verts + b0 * (long long)(NV * 3), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_virt =
+        __builtin_amdgcn_make_buffer_rsrc((vout ? vout : verts) + b0 * (long long)vrow_floats, 0, 0x7fffffff, 0x00020000);
     auto store_one = [&](int t, int g, int r, const f32x16* o3, bool guard) {
         const bool mesh = t < NT;
         const int v = (mesh ? t : t - NT) * 32 + il;
         const long long rstride = mesh ? (long long)(NV * 3) : (long long)vrow_floats;
         const bool vok = t >= 0 && (mesh ? v < NV : (vout != nullptr));
         const int body = (r & 3) + 8 * (r >> 2) + 4 * h;
-        if ((ABL & 1) && o3[0][r] != 12345.678f) return;          // (never true: keeps the arithmetic alive)
         if (vok && (!guard || g * 32 + body < nb)) {
-            const int brow = (ABL & 64) ? (body & 7) : g * 32 + body;      // (ABL & 64: every store of the chip lands in the same 8 rows -- L2-resident)
-            if (SP >= 100) {
-                const unsigned off = (unsigned)((brow * (int)rstride + v * 3) * 4);
-                u32x3 t3 = {__float_as_uint(o3[0][r]), __float_as_uint(o3[1][r]), __float_as_uint(o3[2][r])};
-                if (mesh) __builtin_amdgcn_raw_buffer_store_b96(t3, rs_mesh, off, 0, SP - 100);
-                else __builtin_amdgcn_raw_buffer_store_b96(t3, rs_virt, off, 0, SP - 100);
-            } else {
-                float* o = (mesh ? verts : vout) + (((ABL & 64) ? 0 : b0) + brow) * rstride + (long long)v * 3;
-                if (SP == 1) {
-                    f32x3 t3 = {o3[0][r], o3[1][r], o3[2][r]};
-                    __builtin_nontemporal_store(t3, reinterpret_cast<f32x3*>(o));
-                } else {
-                    o[0] = o3[0][r]; o[1] = o3[1][r]; o[2] = o3[2][r];
-                }
-            }
+            const int brow = g * 32 + body;
+            const unsigned off = (unsigned)((brow * (int)rstride + v * 3) * 4);
+            u32x3 t3 = {__float_as_uint(o3[0][r]), __float_as_uint(o3[1][r]), __float_as_uint(o3[2][r])};
+            if (mesh) __builtin_amdgcn_raw_buffer_store_b96(t3, rs_mesh, off, 0, AUX_NT);
+            else __builtin_amdgcn_raw_buffer_store_b96(t3, rs_virt, off, 0, AUX_NT);
         }
     };
-    auto store_group = [&](int t, int g, const f32x16* o3, bool guard) {
+    auto store_group = [&](int t, int g, const f32x16* o3, bool guard) {      // (the last tile of a wave: nothing left to spread its stores over)
 #pragma unroll
         for (int r = 0; r < 16; ++r) store_one(t, g, r, o3, guard);
     };
 
     half8 ring[R][6];
     int tile = round0 * NWW + wave;
-    if (SV & 2) {                                             // wave w starts w quarter periods (~3 700 cycles each; SV & 8: eighths) late
-        for (int k = 0; k < wave; ++k) __builtin_amdgcn_s_sleep((SV & 8) ? 29 : 58);
-    }
     if (round0 < round1 && tile < ntiles) {
         const half8* q = blend + (long long)tile * (KS * 6 * 64) + lane;
 #pragma unroll
         for (int s = 0; s < PF; ++s) load_step(ring[s], q + s * 384, s);
     }
-    f32x16 outp[2][3];                                        // (SV & 4: the previous tile's results, stored inside this tile's blend phase)
+    f32x16 outp[2][3];                                        // the previous tile's results, stored inside this tile's blend phase
     int ptile = -1;
-    unsigned long long ph_blend = 0, ph_skin0 = 0, ph_skin1 = 0;      // (ABL & 128: shader cycles per phase, summed over this wave's tiles)
     for (int rd = round0; rd < round1; ++rd, tile += NWW) {
         if (tile >= ntiles) break;                           // (wave-uniform: the last round may be ragged)
-        unsigned long long ph_t0 = 0;
-        if (ABL & 128) ph_t0 = __builtin_amdgcn_s_memtime();
         const bool has_next = rd + 1 < round1 && tile + NWW < ntiles;
         const half8* p = blend + (long long)tile * (KS * 6 * 64) + lane;
         const half8* pn = has_next ? p + (long long)NWW * (KS * 6 * 64) : p;      // (no next tile: the head loads re-read this one, unused)
@@ -985,7 +952,7 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             half8 fhn[2] = {fh[0], fh[1]}, fln[2] = {fl[0], fl[1]};
-            if (s + 1 < KS && !(ABL & 32)) {
+            if (s + 1 < KS) {
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
                     fhn[g] = *reinterpret_cast<const half8*>(fh_row + g * 32 * FSH + 16 * (s + 1));
@@ -1009,26 +976,16 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
                 const int g = (j % 6) / 3, cc = j % 3;
                 const half8& fa_ = prod == 2 ? fl[g] : fh[g];
                 const half8& cb_ = c[2 * cc + (prod == 1 ? 1 : 0)];
-                if (!(ABL & 8)) acc[g][cc] = mfma16h(fa_, cb_, (s == 0 && j < 6) ? zero16 : acc[g][cc]);
-                else if (s == 0 && j < 6) { acc[g][cc] = zero16; acc[g][cc][0] = (float)fa_[0] + (float)cb_[1]; }
-                if ((SV & 4) && j + 1 == stride && (s == KS - PF || s == KS - PF + 1) && ptile >= 0) {
-                    // the previous tile's stores: behind this tile's last in-tile request, in front of the next tile's head requests, which are
-                    // not waited for before the skinning phase is over
-                    __builtin_amdgcn_sched_barrier(0);
-                    const int gs = s - (KS - PF);
-                    if (full) store_group(ptile, gs, outp[gs], false);
-                    else store_group(ptile, gs, outp[gs], true);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                acc[g][cc] = mfma16h(fa_, cb_, (s == 0 && j < 6) ? zero16 : acc[g][cc]);
                 if ((j + 1) % stride == 0) {
                     const int f = (j + 1) / stride - 1;      // 0..5
                     __builtin_amdgcn_sched_barrier(0);
-                    if ((in_tile || head) && !(PD16 && ks_l >= 1 && (f & 1)) && !(ABL & 2)) slot[f] = src[f * 64];
-                    if ((SV & 16) && (f & 1) && s * 3 + f / 2 < 32) {      // the previous tile's 32 stores, three per k-step: a steady write stream instead of a burst
+                    if ((in_tile || head) && !(PD16 && ks_l >= 1 && (f & 1))) slot[f] = src[f * 64];
+                    if ((f & 1) && s * 3 + f / 2 < 32) {      // the previous tile's 32 stores, three per k-step: a steady write stream instead of a burst
                         const int idx = s * 3 + f / 2;
                         store_one(ptile, idx >> 4, idx & 15, outp[idx >> 4], !full);
                     }
-                    if (s == ((SV & 4) ? KS - PF - 2 : KS - 3) && f < KSP) sw[f] = sp[f * 64];      // this tile's packed skinning weights: needed right after the contraction (SV & 4: requested in front of the delayed stores)
+                    if (s == KS - 3 && f < KSP) sw[f] = sp[f * 64];      // this tile's packed skinning weights: needed right after the contraction
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -1041,10 +998,9 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
             bool in_loop = false;
 #pragma unroll
             for (int s2 = KS - PF; s2 < KS; ++s2) in_loop = in_loop || ((s2 + R - 1) % R == j);
-            if (!in_loop && !(ABL & 2)) load_step(ring[j], pn + j * 384, j);
+            if (!in_loop) load_step(ring[j], pn + j * 384, j);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (ABL & 128) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph_blend += t - ph_t0; ph_t0 = t; }
         // ---------------- skinning on the matrix pipe, K-packed: T_e[body][vertex] = [Ah | Al | Ah | -][body] . [Wh | Wh | Wl | 0][vertex] ----------------
         // Software pipeline over the twelve entries: [LDS operands of e + 1] -> [5-MFMA chain of e into one of two result buffers] -> [fold of
         // e - 1 from the other buffer on the VALU while that chain runs].  out_c = (T[4c] x + T[4c+1] y + T[4c+2] z) us_rot + T[4c+3] us_w.
@@ -1059,17 +1015,15 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
             for (int q = 0; q < 3; ++q) { a[q] = *reinterpret_cast<const half8*>(ar + 16 * q); an[q] = a[q]; }
             f32x16 T[2], fa = zero16;                         // (two result buffers, alternating)
             f32x16 out[3];
-            if (!TV || (ABL & 4)) { T[0] = zero16; T[1] = zero16; }
+            if (!TV) { T[0] = zero16; T[1] = zero16; }
 #pragma unroll
             for (int e = 0; e <= 12; ++e) {
-                if (e + 1 < 12 && !(ABL & 32)) {
+                if (e + 1 < 12) {
 #pragma unroll
                     for (int q = 0; q < 3; ++q) an[q] = *reinterpret_cast<const half8*>(ar + (e + 1) * WB * ASP + 16 * q);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (ABL & 4) {
-                    if (e < 12) T[e & 1][0] += (float)a[0][0] + (float)a[1][1] + (float)a[2][2] + (float)sw[e % KSP][3];
-                } else if (TV) {
+                if (TV) {
                     if (e < 12) mfma16h_v01(T[e & 1], a[0], sw[0], a[1], sw[1]);
                     else asm volatile("s_nop 11");
                     __builtin_amdgcn_sched_barrier(0);
@@ -1085,13 +1039,7 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
                 if (e > 0) {                                  // fold entry e - 1 while the chain above is in the pipe
                     const int pe = e - 1, c = pe >> 2, q = pe & 3;
                     const f32x16& Tp = T[pe & 1];
-                    if (ABL & 16) {
-                        if (q == 3) {
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) out[c][r] = Tp[r];
-                            out[c][0] += acc[g][c][0];
-                        }
-                    } else if (q == 0) {
+                    if (q == 0) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) fa[r] = Tp[r] * acc[g][0][r];
                     } else if (q == 1) {
@@ -1110,20 +1058,15 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
 #pragma unroll
                 for (int q = 0; q < 3; ++q) a[q] = an[q];
             }
-            // (lane = vertex, register r = body (r&3) + 8 (r>>2) + 4 h of group g: sixteen 12-byte stores per lane, straight from the registers)
-            if (SV & (4 | 16)) {
+            // (lane = vertex, register r = body (r&3) + 8 (r>>2) + 4 h of group g: sixteen 12-byte stores per lane, straight from the registers,
+            //  issued during the NEXT tile's blend phase -- or below, for the last tile)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) outp[g][c] = out[c];
-            } else {
-                if (full) store_group(tile, g, out, false);
-                else store_group(tile, g, out, true);
-            }
+            for (int c = 0; c < 3; ++c) outp[g][c] = out[c];
             __builtin_amdgcn_sched_barrier(0);
-            if (ABL & 128) { const unsigned long long t = __builtin_amdgcn_s_memtime(); (g ? ph_skin1 : ph_skin0) += t - ph_t0; ph_t0 = t; }
         }
         ptile = tile;
     }
-    if ((SV & (4 | 16)) && ptile >= 0) {
+    if (ptile >= 0) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             if (full) store_group(ptile, g, outp[g], false);
@@ -1133,9 +1076,6 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
     if (clk && blockIdx.x == 0 && threadIdx.x == 0) {
         atomicAdd(clk, (unsigned long long)__builtin_amdgcn_s_memtime() - clk_c0);
         atomicAdd(clk + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime() - clk_w0);
-    }
-    if ((ABL & 128) && clk && lane == 0 && (blockIdx.x % 61) == 0) {      // (tools: a sample of the workgroups; clk points at >= 6 counters then)
-        atomicAdd(clk + 2, ph_blend); atomicAdd(clk + 3, ph_skin0); atomicAdd(clk + 4, ph_skin1); atomicAdd(clk + 5, (unsigned long long)(round1 - round0));
     }
 }
 
@@ -1238,29 +1178,12 @@ extern "C" int straps_smpl_fwd(const straps_smpl_model_t* model, const float* be
     int rc = straps_smpl_launch_pose(model, betas, rotmats, F, Amat, joints, batch, st);
     if (rc != STRAPS_OK) return rc;
     const int split = mode == STRAPS_SMPL_SPLIT_F16 ? 1 : mode == STRAPS_SMPL_SPLIT_F16_LBS ? 2 : 0;
-    // measurement knobs of the TOOLS build (tools/smpl_ablate.sh; the product library never reads the environment): STRAPS_SMPL_PF = depth of
-    // the fragment ring (default 3 for the blend-split kernel, 2 for the matrix-pipe-skinning kernel), STRAPS_SMPL_ABLATE (compile-time
-    // ablations of the latter), STRAPS_SMPL_RPC (rounds per workgroup)
-    static const int pf_env = STRAPS_TOOL_ENV_INT("STRAPS_SMPL_PF", 0), rpc_env = STRAPS_TOOL_ENV_INT("STRAPS_SMPL_RPC", 0);
-    const int pf = pf_env >= 1 && pf_env <= 4 ? pf_env : (split == 2 ? 2 : 3);
-    constexpr int nwv = 8;              // (12 / 16 waves per workgroup need <= 168 / 128 VGPRs: the kernel spills and runs 3.5x slower)
-    auto h_kernel = pf == 1 ? smpl_verts_h_kernel<1> : pf == 2 ? smpl_verts_h_kernel<2> : pf == 4 ? smpl_verts_h_kernel<4> : smpl_verts_h_kernel<3>;
-    auto hh_kernel = pd16 == 1 ? (pf == 1 ? smpl_verts_hh_kernel<8, 1, 0, 1> : smpl_verts_hh_kernel<8, 2, 0, 1>)
-                   : pd16 == 2 ? (pf == 1 ? smpl_verts_hh_kernel<8, 1, 0, 2> : smpl_verts_hh_kernel<8, 2, 0, 2>)
-                   : pf == 1 ? smpl_verts_hh_kernel<8, 1, 0> : smpl_verts_hh_kernel<8, 2, 0>;      // (a deeper ring does not fit: PF = 2 uses 255 of the 256 registers two waves per SIMD leave a wave)
-#ifdef STRAPS_TOOLS
-    {   // ablation instantiations (wrong results by design; tools/smpl_ablate.sh) -- tools build only
-        static const int ablate = STRAPS_TOOL_ENV_INT("STRAPS_SMPL_ABLATE", 0);
-        if (!pd16 && ablate)
-            hh_kernel = ablate == 1 ? smpl_verts_hh_kernel<8, 1, 1> : ablate == 2 ? smpl_verts_hh_kernel<8, 1, 2> : ablate == 3 ? smpl_verts_hh_kernel<8, 1, 3>
-                      : ablate == 7 ? smpl_verts_hh_kernel<8, 1, 7> : ablate == 15 ? smpl_verts_hh_kernel<8, 1, 15> : hh_kernel;
-    }
-#endif
+    auto hh_kernel = pd16 == 1 ? smpl_verts_hh_kernel<1> : pd16 == 2 ? smpl_verts_hh_kernel<2> : smpl_verts_hh_kernel<0>;
     const size_t lds = split == 2 ? (size_t)(2 * BT * FSH + 12 * BT * ASP) * sizeof(_Float16)
                                   : (size_t)(BT * (split ? FSH : FS) + BT * AS + NW * BT * HS + NW * 256) * sizeof(float);
-    static unsigned long long lds_raised[5] = {0, 0, 0, 0, 0};          // per kernel variant: bit mask of the devices done
+    static unsigned long long lds_raised[5] = {0, 0, 0, 0, 0};          // per kernel (exact, h, hh<0..2>): bit mask of the devices done
     {
-        hipError_t e = straps_raise_dynamic_lds(split == 2 ? (const void*)hh_kernel : split ? (const void*)h_kernel : (const void*)smpl_verts_kernel,
+        hipError_t e = straps_raise_dynamic_lds(split == 2 ? (const void*)hh_kernel : split ? (const void*)smpl_verts_h_kernel : (const void*)smpl_verts_kernel,
                                                 lds, lds_raised[split + pd16]);
         if (e != hipSuccess) { straps_set_error("smpl_verts_kernel: cannot raise dynamic LDS to %zu: %s", lds, hipGetErrorString(e)); return STRAPS_EHIP; }
     }
@@ -1281,68 +1204,32 @@ extern "C" int straps_smpl_fwd(const straps_smpl_model_t* model, const float* be
         int nchw = chunks > 0 ? chunks : (int)((256 + bgroups - 1) / bgroups);
         if (nchw > rounds_w) nchw = rounds_w;
         if (nchw < 1) nchw = 1;
-        const int rpcw = rpc_env > 0 ? (rpc_env > rounds_w ? rounds_w : rpc_env) : (rounds_w + nchw - 1) / nchw;
+        const int rpcw = (rounds_w + nchw - 1) / nchw;
         nchw = (rounds_w + rpcw - 1) / rpcw;
         if (bgroups * nchw > 0x7fffffffLL) {
             straps_set_error("straps_smpl_fwd: batch %lld exceeds one launch; split it", batch);
             return STRAPS_EUNSUPPORTED;
         }
-        // product form (tools/smpl_w_ab.py, profiles/r04_smpl_w_ab.txt): prefetch distance 3, skinning chains with VGPR results, the previous tile's
-        // stores spread over the blend phase as non-temporal buffer stores.  The tools build selects the A/B instantiations:
-        // STRAPS_SMPL_WVAR = 10 * PF + TV (plain stores at the tile end), STRAPS_SMPL_WSV (store forms), STRAPS_SMPL_WABL (ablations, wrong results)
-        constexpr int B_NT = (100 + 2) << 8, SV_PRODUCT = 16 | B_NT;
-        auto w_kernel = pd16 == 1 ? smpl_verts_w_kernel<3, 1, 1, 0, SV_PRODUCT> : pd16 == 2 ? smpl_verts_w_kernel<3, 2, 1, 0, SV_PRODUCT>
-                      : smpl_verts_w_kernel<3, 0, 1, 0, SV_PRODUCT>;
-        int wslot = pd16;
-        if (wide_builtin) {      // (the builtin-MFMA reference instantiation: TV = 0, otherwise the product form)
-            w_kernel = smpl_verts_w_kernel<3, 0, 0, 0, SV_PRODUCT>;
-            wslot = 6;
-        }
-#ifdef STRAPS_TOOLS
-        static const int wvar = STRAPS_TOOL_ENV_INT("STRAPS_SMPL_WVAR", 0);
-        if (!pd16 && wvar) {
-            w_kernel = wvar == 31 ? smpl_verts_w_kernel<3, 0, 1> : wvar == 30 ? smpl_verts_w_kernel<3, 0, 0> : wvar == 21 ? smpl_verts_w_kernel<2, 0, 1>
-                     : wvar == 41 ? smpl_verts_w_kernel<4, 0, 1> : smpl_verts_w_kernel<4, 0, 0>;
-            wslot = 3;
-        }
-        static const int wsv = STRAPS_TOOL_ENV_INT("STRAPS_SMPL_WSV", 0);      // store forms: SV bits | form << 8
-        if (!pd16 && wsv) {
-            constexpr int NT1 = 1 << 8, B_SYS = (100 + 19) << 8, B_PLAIN = 100 << 8;
-            w_kernel = wsv == 1 ? smpl_verts_w_kernel<3, 0, 1, 0, NT1> : wsv == 2 ? smpl_verts_w_kernel<3, 0, 1, 0, 16> : wsv == 3 ? smpl_verts_w_kernel<3, 0, 1, 0, 16 | NT1>
-                     : wsv == 4 ? smpl_verts_w_kernel<3, 0, 1, 0, B_NT> : wsv == 5 ? smpl_verts_w_kernel<3, 0, 1, 0, B_SYS> : wsv == 7 ? smpl_verts_w_kernel<3, 0, 1, 0, B_PLAIN>
-                     : wsv == 10 ? smpl_verts_w_kernel<3, 0, 1, 0, 4 | NT1> : wsv == 12 ? smpl_verts_w_kernel<4, 0, 1, 0, B_NT> : wsv == 13 ? smpl_verts_w_kernel<4, 0, 1, 0, 16 | B_NT>
-                     : wsv == 16 ? smpl_verts_w_kernel<5, 0, 1, 0, B_NT> : smpl_verts_w_kernel<2, 0, 1, 0, 16 | B_NT>;
-            wslot = 4;
-        }
-        static const int wabl = STRAPS_TOOL_ENV_INT("STRAPS_SMPL_WABL", 0);
-        if (!pd16 && wabl) {
-            w_kernel = wabl == 1 ? smpl_verts_w_kernel<3, 0, 1, 1> : wabl == 2 ? smpl_verts_w_kernel<3, 0, 1, 2> : wabl == 3 ? smpl_verts_w_kernel<3, 0, 1, 3>
-                     : wabl == 4 ? smpl_verts_w_kernel<3, 0, 1, 4> : wabl == 8 ? smpl_verts_w_kernel<3, 0, 1, 8> : wabl == 12 ? smpl_verts_w_kernel<3, 0, 1, 12>
-                     : wabl == 15 ? smpl_verts_w_kernel<3, 0, 1, 15> : wabl == 16 ? smpl_verts_w_kernel<3, 0, 1, 16> : wabl == 32 ? smpl_verts_w_kernel<3, 0, 1, 32>
-                     : wabl == 64 ? smpl_verts_w_kernel<3, 0, 1, 64> : wabl == 66 ? smpl_verts_w_kernel<3, 0, 1, 66> : wabl == 128 ? smpl_verts_w_kernel<3, 0, 1, 128, SV_PRODUCT>
-                     : wabl == 129 ? smpl_verts_w_kernel<3, 0, 1, 129, SV_PRODUCT> : wabl == 130 ? smpl_verts_w_kernel<3, 0, 1, 130, SV_PRODUCT>
-                     : wabl == 131 ? smpl_verts_w_kernel<3, 0, 1, 131, SV_PRODUCT> : wabl == 151 ? smpl_verts_w_kernel<3, 0, 1, 151, SV_PRODUCT>
-                     : wabl == 183 ? smpl_verts_w_kernel<3, 0, 1, 183, SV_PRODUCT> : wabl == 135 ? smpl_verts_w_kernel<3, 0, 1, 135, SV_PRODUCT>
-                     : smpl_verts_w_kernel<3, 0, 1, 63>;
-            wslot = 5;      // (one variant per process: the switches are read once)
-        }
-#endif
+        // product form (profiles/r04_smpl_w_ab.txt): prefetch distance 3, skinning chains with VGPR results, the previous tile's stores spread
+        // over the blend phase as non-temporal buffer stores.  wide_builtin: the same with builtin MFMAs in the skinning chains, the reference.
+        auto w_kernel = wide_builtin ? smpl_verts_w_kernel<0, 0> : pd16 == 1 ? smpl_verts_w_kernel<1, 1> : pd16 == 2 ? smpl_verts_w_kernel<2, 1>
+                      : smpl_verts_w_kernel<0, 1>;
         const size_t ldsw = (size_t)(2 * WB * FSH + 12 * WB * ASP) * sizeof(_Float16);
-        static unsigned long long lds_raised_w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        hipError_t e = straps_raise_dynamic_lds((const void*)w_kernel, ldsw, lds_raised_w[wslot]);
+        static unsigned long long lds_raised_w[4] = {0, 0, 0, 0};      // per kernel (w<0..2, 1>, w<0, 0>)
+        hipError_t e = straps_raise_dynamic_lds((const void*)w_kernel, ldsw, lds_raised_w[wide_builtin ? 3 : pd16]);
         if (e != hipSuccess) { straps_set_error("smpl_verts_w_kernel: cannot raise dynamic LDS to %zu: %s", ldsw, hipGetErrorString(e)); return STRAPS_EHIP; }
         hipLaunchKernelGGL(w_kernel, dim3((unsigned)(bgroups * nchw)), dim3(NWW * 64), ldsw, st, *model, F, Amat, verts, joints ? vout : nullptr,
                            batch, (int)bgroups, ntiles, rounds_w, rpcw, straps_clk_acc_current());
     } else if (split == 2) {
-        // own round structure: nwv tiles per round, ragged last round
+        // own round structure: NW tiles per round, ragged last round
         const int ntiles = joints ? model->n_tiles : NT;
-        const int rounds2 = (ntiles + nwv - 1) / nwv;
-        const int rpc2 = rpc_env > 0 ? (rpc_env > rounds2 ? rounds2 : rpc_env) : resolve_rpc(rounds2, batch, chunks);
+        const int rounds2 = (ntiles + NW - 1) / NW;
+        const int rpc2 = resolve_rpc(rounds2, batch, chunks);
         const int nch2 = (rounds2 + rpc2 - 1) / rpc2;
-        hipLaunchKernelGGL(hh_kernel, dim3((unsigned)(btiles * nch2)), dim3(nwv * 64), lds, st, *model, F, Amat, verts, joints ? vout : nullptr,
+        hipLaunchKernelGGL(hh_kernel, dim3((unsigned)(btiles * nch2)), dim3(NW * 64), lds, st, *model, F, Amat, verts, joints ? vout : nullptr,
                            batch, (int)btiles, ntiles, rounds2, rpc2, straps_clk_acc_current());
     } else if (split)
-        hipLaunchKernelGGL(h_kernel, dim3((unsigned)(btiles * nch)), dim3(NW * 64), lds, st, *model, F, Amat, verts,
+        hipLaunchKernelGGL(smpl_verts_h_kernel, dim3((unsigned)(btiles * nch)), dim3(NW * 64), lds, st, *model, F, Amat, verts,
                            joints ? vout : nullptr, batch, (int)btiles, rounds, rpc);
     else
         hipLaunchKernelGGL(smpl_verts_kernel, dim3((unsigned)(btiles * nch)), dim3(NW * 64), lds, st, *model, F, Amat, verts,

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """tools/smpl_w_ab.py -- A/B of the SMPL vertex kernels of mode fp16x3_lbs on one box: the 32-body kernel (narrow: smpl_verts_hh_kernel) against
-the 64-body kernel (wide: smpl_verts_w_kernel) and the tools-build instantiations of the latter (STRAPS_SMPL_WVAR = 10 * PF + TV, STRAPS_SMPL_WSV = store forms, STRAPS_SMPL_WABL = ablations; one
-process per variant: the switch is read once).  Every variant is first checked against the float64 oracle (ragged batch through the
-forced kernel), then timed at 65 536 bodies with joints, HIP events around `iters` back-to-back calls.
+the 64-body kernel (wide: smpl_verts_w_kernel) and, for mode fp16x3_lbs, its builtin-MFMA reference form (wide_builtin), one process each.
+Every kernel is first checked against the float64 oracle (ragged batch through the forced kernel), then timed at 65 536 bodies with joints,
+HIP events around `iters` back-to-back calls.  (The store-form / prefetch-depth / ablation instantiations of round 4 are retired: their
+results are profiles/r04_smpl_w_ab.txt, the last commit that built them is 92619b1.)
 
-    python tools/smpl_w_ab.py [--variants 31,30,21,41] [--iters 12] [--batch 65536] [--modes fp16x3_lbs,fp16x3_lbs_p16]
+    python tools/smpl_w_ab.py [--iters 12] [--batch 65536] [--modes fp16x3_lbs,fp16x3_lbs_p16] [--sweep]
 """
 import argparse
 import os
@@ -20,17 +21,14 @@ def child(args):
     import torch
     import straps_amd
     from straps_amd import hipabi
-    if args.tools_lib:
-        hipabi.use_library(hipabi.build(tools=True))
     import straps_oracle as O
     from detgen import det_uniform
     dev = torch.device('cuda:0')
     model = straps_amd.synthetic_smpl_model(0)
     smpl = straps_amd.SMPL(model, batch_size=1).to(dev)
-    tag = 'WVAR=%s WABL=%s WSV=%s %s %s' % (os.environ.get('STRAPS_SMPL_WVAR', '-'), os.environ.get('STRAPS_SMPL_WABL', '-'), os.environ.get('STRAPS_SMPL_WSV', '-'),
-                                            args.kernel, args.mode)
+    tag = '%s %s' % (args.kernel, args.mode)
     # ---- parity: ragged batch (groups of 64: 70 -> one full + 6 bodies; 2048 + 37), incl. an extreme body, vs float64 ----
-    for Bp in (() if os.environ.get('STRAPS_SMPL_WABL') else (70, 2085)):      # (ablations compute wrong results: timing only)
+    for Bp in (70, 2085):
         betas = torch.from_numpy(det_uniform((Bp, 10), 100 + Bp, -2.5, 2.5))
         betas[0] = torch.tensor([10.0, -8.0, 6.0, 4.0, -4.0, 3.0, 3.0, -3.0, 2.0, 2.0])
         aa = torch.from_numpy(det_uniform((Bp, 72), 200 + Bp, -0.9, 0.9))
@@ -54,7 +52,7 @@ def child(args):
         smpl.forward_arrays(betas, R, precision=args.mode, kernel=args.kernel, out_verts=verts, out_joints=joints)
     torch.cuda.synchronize()
     L = hipabi.lib()
-    clk = torch.zeros(8, dtype=torch.int64, device=dev)      # (shader ticks, wall ticks) of workgroup 0 of every vertex-kernel launch (+ WABL & 128: phase cycles)
+    clk = torch.zeros(2, dtype=torch.int64, device=dev)      # (shader ticks, wall ticks) of workgroup 0 of every vertex-kernel launch
     hipabi.check(L.straps_set_clock_accumulator(hipabi.ptr(clk)), 'straps_set_clock_accumulator')
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
@@ -64,13 +62,9 @@ def child(args):
     torch.cuda.synchronize()
     ms = s.elapsed_time(e) / args.iters
     hipabi.check(L.straps_set_clock_accumulator(None), 'straps_set_clock_accumulator')
-    cl = [int(v) for v in clk.tolist()]
-    c, w = cl[0], cl[1]
+    c, w = (int(v) for v in clk.tolist())
     mhz = c / w * L.straps_wall_clock_khz() / 1e3 if w > 0 else 0.0
     print('%s  B=%d  %.3f ms/call  %.2f M bodies/s  HBM frac %.3f  sclk %.0f MHz' % (tag, B, ms, B / ms / 1e3, B * 84664.0 / (ms * 1e-3) / 8e12, mhz))
-    if cl[5]:      # (WABL & 128) shader cycles per tile and phase, averaged over the sampled waves: ideal = 252 x 32 = 8064 (blend), 60 x 32 = 1920 per skinning group
-        print('%s  cycles per tile: blend %.0f (MFMA floor 8064)  skin g0 %.0f  skin g1 %.0f (floor 1920 each)  total %.0f (floor 11904)'
-              % (tag, cl[2] / cl[5], cl[3] / cl[5], cl[4] / cl[5], (cl[2] + cl[3] + cl[4]) / cl[5]))
 
 
 def sweep(args):
@@ -103,10 +97,6 @@ def sweep(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--variants', default='31,30,21,41')
-    ap.add_argument('--ablate', default='', help='comma list of STRAPS_SMPL_WABL values (tools build; timing only): 1 no stores, 2 no fragment '
-                    'loads, 4 no skinning chains, 8 no blend MFMAs, 16 no fold, 32 no LDS operand reads (3, 12, 15, 31, 63 = sums)')
-    ap.add_argument('--sv', default='', help='comma list of STRAPS_SMPL_WSV values (tools build): 1 non-temporal stores, 2 staggered waves, 4 stores delayed into the next blend phase; sums')
     ap.add_argument('--modes', default='fp16x3_lbs')
     ap.add_argument('--iters', type=int, default=12)
     ap.add_argument('--batch', type=int, default=65536)
@@ -114,7 +104,6 @@ def main():
     ap.add_argument('--sweep', action='store_true', help='narrow vs wide over batch sizes (product library), then exit')
     ap.add_argument('--kernel', default='wide')
     ap.add_argument('--mode', default='fp16x3_lbs')
-    ap.add_argument('--tools-lib', action='store_true')
     args = ap.parse_args()
     if args.child:
         return child(args)
@@ -122,16 +111,9 @@ def main():
         return sweep(args)
     base = [sys.executable, os.path.abspath(__file__), '--child', '--iters', str(args.iters), '--batch', str(args.batch)]
     for mode in args.modes.split(','):
-        # product library: narrow and wide as shipped
-        for kern in ('narrow', 'wide'):
+        # narrow and wide as shipped; wide_builtin (the builtin-MFMA reference of the skinning chains) exists for mode fp16x3_lbs only
+        for kern in ('narrow', 'wide') + (('wide_builtin',) if mode == 'fp16x3_lbs' else ()):
             subprocess.run(base + ['--kernel', kern, '--mode', mode], timeout=600)
-        if mode == 'fp16x3_lbs':
-            for v in [x for x in args.variants.split(',') if x]:
-                subprocess.run(base + ['--kernel', 'wide', '--mode', mode, '--tools-lib'], env=dict(os.environ, STRAPS_SMPL_WVAR=v), timeout=600)
-            for v in [x for x in args.sv.split(',') if x]:
-                subprocess.run(base + ['--kernel', 'wide', '--mode', mode, '--tools-lib'], env=dict(os.environ, STRAPS_SMPL_WSV=v), timeout=600)
-            for v in [x for x in args.ablate.split(',') if x]:
-                subprocess.run(base + ['--kernel', 'wide', '--mode', mode, '--tools-lib'], env=dict(os.environ, STRAPS_SMPL_WABL=v), timeout=600)
 
 
 if __name__ == '__main__':

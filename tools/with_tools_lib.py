@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Run a script of this repository against the TOOLS build of the library (tools/bin/libstraps_hip_tools.so, compiled with
 -DSTRAPS_TOOLS): the build that carries the ablation instantiations -- which compute WRONG results by design -- and honours the
-STRAPS_* A/B environment switches (STRAPS_SMPL_ABLATE, STRAPS_SMPL_PF, STRAPS_SMPL_RPC, STRAPS_WGRAD3_ABL, STRAPS_WGRAD_*,
-STRAPS_STEM_WGRAD_*).  The product library has none of them and never reads the environment.
+STRAPS_* A/B environment switches (STRAPS_WGRAD3_ABL, STRAPS_WGRAD_*, STRAPS_STEM_WGRAD_*, STRAPS_X3_*, ...).  The product library has none of them and never reads the environment.
 
     python tools/with_tools_lib.py bench.py --config 4 --no-cpu-baseline
 """
