@@ -752,6 +752,34 @@ int straps_crop_resize(const float* seg, const float* joints2d, const float* uni
                        double delta_centre_lo, double delta_centre_hi, float* out_seg,
                        float* out_joints2d, int* boxes, int batch, int wh, int out_wh, int nj,
                        void* stream);
+/* The predict-side front end (csrc/predict.hip; predict/predict_3D.py:116-126 for a batch): detector silhouettes and 2-D keypoints ->
+ * the regressor's proxy input, as crop_and_resize_silhouette_joints (utils/image_utils.py:108-163) + create_proxy_representation
+ * (predict_3D.py:67-76) + the numpy convert_2Djoints_to_gaussian_heatmaps (utils/label_conversions.py:58-87) compute it per image.
+ *   sil [B][h][w] uint8 (0 = background), joints2d [B][nj][ld_joint] fp32 with columns (x, y, ...): ld_joint >= 2, later columns (a
+ *   confidence) are skipped; gauss_patch [4*std][4*std] fp32, the reference's truncated Gaussian, supplied by the caller (predict.py
+ *   heatmap_patch builds it with the reference's own float64 numpy expressions, which makes the heat maps bit-identical; the library
+ *   evaluates no exp);  out_nchw [B][1+nj][out_wh][out_wh], out_joints2d [B][nj][2], boxes [B][6] = {wr0, wc0, wr1, wc1, valid, 0}.
+ * Per sample, box arithmetic in double, unfused:
+ *   window: (rmin, rmax, cmin, cmax) over sil != 0; centre ((rmin+rmax)/2.0, (cmin+cmax)/2.0); side = max(rmax-rmin, cmax-cmin) *
+ *     bbox_scale_factor; (wr0, wc0, wr1, wc1) = int16 truncation toward zero of (cr - side/2, cc - side/2, cr + side/2, cc + side/2),
+ *     NOT clamped (straps_crop_resize clamps); ch = wr1 - wr0, cw = wc1 - wc0.  Rows [wr0, wr1) x cols [wc0, wc1) are read with zeros
+ *     outside the frame: the reference's crop of the clamped box followed by copyMakeBorder.
+ *   channel 0: out[y][x] = (float)sil[wr0 + sy][wc0 + sx] or 0 outside the frame, sy = min(floor(y * (1.0 / ((double)out_wh / ch))),
+ *     ch - 1), sx likewise with cw (cv2.INTER_NEAREST as OpenCV computes it); the value passes through.
+ *   joints: x' = (double)((float)x - (float)wc0) * ((double)out_wh / cw), y' with wr0 and ch; out_joints2d = (float)(x', y').
+ *   channel 1 + j: the reference's heat map around (int16 truncation of x', of y'): nothing unless both exceed -2 std and stay below
+ *     out_wh - 1 + 2 std; rows [max(0, jy - 2 std), min(out_wh - 1, jy + 2 std)) and the same columns receive
+ *     gauss_patch[y - jy + 2 std][x - jx + 2 std]; zero elsewhere.
+ *   invalid sample (empty silhouette, or ch <= 0 or cw <= 0: the reference raises): valid = 0 and every output element of the sample,
+ *     its joints included, is written as 0.
+ *   Window or scaled joint values beyond int16 are outside the contract.
+ * Every output element is stored exactly once (no memset, no scatter); nothing is allocated or synchronised, so the call can be captured
+ * into a hipGraph.  Checked before any HIP call (STRAPS_EINVAL, straps_last_error() names the argument): non-null pointers; batch, h, w,
+ * nj, std > 0; h, w < 32768; ld_joint >= 2; out_wh % 4 == 0; out_nchw 16-byte aligned.                                                */
+int straps_predict_proxy_input(const uint8_t* sil, const float* joints2d, int ld_joint,
+                               const float* gauss_patch, int std, double bbox_scale_factor,
+                               float* out_nchw, float* out_joints2d, int32_t* boxes,
+                               int batch, int h, int w, int nj, int out_wh, void* stream);
 /* On-device evaluation metrics (metrics/train_loss_and_metrics_tracker.py:127-197 +
  * utils/eval_utils.py:7-85): for each sample b, out3[b] = { sum_n |p-t|,
  * sum_n |scale_and_translation_transform(p) - t|, sum_n |procrustes(p) - t| } over npoints 3-D points

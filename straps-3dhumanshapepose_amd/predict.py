@@ -1,0 +1,119 @@
+"""The predict path for a batch, on the device (reference predict/predict_3D.py:116-149, run_predict.py).
+
+The reference turns each image's detector outputs -- a silhouette and 17 keypoints -- into the regressor's 18-channel input on the
+host, in numpy and cv2: `crop_and_resize_silhouette_joints` (utils/image_utils.py:108-163), `create_proxy_representation`
+(predict_3D.py:67-76) and the numpy `convert_2Djoints_to_gaussian_heatmaps` (utils/label_conversions.py:58-87).  Here that is one
+library call for the whole batch (straps_predict_proxy_input, csrc/predict.hip) on tensors that are already on the GPU, and
+`Predictor` chains it with the one-call regressor, the SMPL forward and the orthographic projection.
+
+These are the PREDICT-side semantics, not the training-side ones of image_utils.batch_crop_and_resize / label_conversions: the window
+is not clamped to the frame (what sticks out reads as zero, and the joints are shifted by the unclamped corner), and the heat maps are
+the numpy ones (float64 joints truncated to int16, a float64 Gaussian).  The detectors, pad_to_square, the resize of the RGB image and
+all visualisation are not part of this package.
+"""
+import numpy as np
+import torch
+
+from . import cam_utils, config, hipabi
+from .infer import InferenceRegressor
+
+_PATCHES = {}
+
+
+def heatmap_patch(std=4):
+    """-> [4 std, 4 std] float32 numpy array: the truncated Gaussian of utils/label_conversions.py:68-71, computed as there (float64
+    linspace, sqrt, exp) and cast as numpy casts it on assignment into the float32 heat map -- hence bit-identical heat maps."""
+    std = int(std)
+    if std <= 0:
+        raise ValueError('heatmap_patch: std must be positive (got %r)' % (std,))
+    # 4 std samples of [-2 std, 2 std] per axis; the distance goes through sqrt and is squared again, as there: x^2 + y^2 directly
+    # would differ in the last bit
+    t = np.linspace(-2 * std, 2 * std, 4 * std)
+    dist = np.sqrt(t[None, :] * t[None, :] + t[:, None] * t[:, None])
+    return np.exp(-(dist ** 2 / (2.0 * std ** 2))).astype(np.float32)
+
+
+def _device_patch(device, std):
+    """the patch on `device`, cached per (device, std).  The first use copies from the host: make it outside a graph capture."""
+    key = (str(device), int(std))
+    if key not in _PATCHES:
+        _PATCHES[key] = torch.from_numpy(heatmap_patch(std)).to(device)
+    return _PATCHES[key]
+
+
+@hipabi.on_tensor_device
+def create_proxy_representation_batch(silhouettes, joints2D, out_wh=config.REGRESSOR_IMG_WH, bbox_scale_factor=1.2, std=4):
+    """silhouettes [B,H,W] (GPU; uint8, bool, or a float tensor of integer labels 0..255; 0 = background), joints2D [B,J,2] or [B,J,3]
+    (GPU float; a confidence column is ignored) -> (proxy_rep [B,1+J,out_wh,out_wh] float32, joints2D_cropped [B,J,2] float32,
+    boxes [B,6] int32 = {wr0, wc0, wr1, wc1, valid, 0}).
+
+    Per sample exactly what the reference's crop_and_resize_silhouette_joints + create_proxy_representation compute.  Where the
+    reference raises (an empty silhouette; a window that truncates to zero height or width, e.g. a one-pixel silhouette) the sample's
+    `valid` is 0 and its proxy and joints are all zeros.  Never synchronises; runs on the current stream; capturable."""
+    hipabi.require_gpu_tensor(silhouettes, 'silhouettes')
+    hipabi.require_gpu_tensor(joints2D, 'joints2D')
+    if silhouettes.dim() != 3:
+        raise RuntimeError('create_proxy_representation_batch: silhouettes must be [B,H,W], got %s' % (tuple(silhouettes.shape),))
+    B, H, W = silhouettes.shape
+    if joints2D.dim() != 3 or joints2D.shape[0] != B or joints2D.shape[2] not in (2, 3):
+        raise RuntimeError('create_proxy_representation_batch: joints2D must be [%d,J,2] or [%d,J,3], got %s' % (B, B, tuple(joints2D.shape)))
+    if silhouettes.dtype not in (torch.uint8, torch.bool) and not silhouettes.dtype.is_floating_point:
+        raise RuntimeError('create_proxy_representation_batch: silhouettes must be uint8, bool or float (got %s)' % silhouettes.dtype)
+    dev = silhouettes.device
+    sil = silhouettes.to(torch.uint8).contiguous()
+    j = joints2D.float().contiguous()
+    nj = j.shape[1]
+    patch = _device_patch(dev, std)
+    out = torch.empty(B, 1 + nj, out_wh, out_wh, device=dev, dtype=torch.float32)
+    jout = torch.empty(B, nj, 2, device=dev, dtype=torch.float32)
+    boxes = torch.empty(B, 6, device=dev, dtype=torch.int32)
+    hipabi.check(hipabi.lib().straps_predict_proxy_input(hipabi.ptr(sil), hipabi.ptr(j), j.shape[2], hipabi.ptr(patch), int(std),
+                                                         float(bbox_scale_factor), hipabi.ptr(out), hipabi.ptr(jout), hipabi.ptr(boxes),
+                                                         B, H, W, nj, int(out_wh), hipabi.stream_ptr()), 'straps_predict_proxy_input')
+    return out, jout, boxes
+
+
+class Predictor:
+    """predict_3D.py:116-149 for a batch: `Predictor(regressor, smpl)(silhouettes, joints2D)` -> dict of device tensors.
+
+    regressor: a SingleInputRegressor (wrapped in an InferenceRegressor with `precision`) or an InferenceRegressor; smpl: the SMPL
+    module on the same GPU.  Only existing entry points are composed -- create_proxy_representation_batch, InferenceRegressor(...,
+    rotmats=True), SMPL.forward_arrays, cam_utils -- so every result equals that composition written by hand, bit for bit.  No call
+    synchronises; after one warm-up call at the same shapes the call can be captured in `torch.cuda.graph`.  After the regressor's
+    weights change, `refresh()`."""
+
+    def __init__(self, regressor, smpl, precision=None, out_wh=config.REGRESSOR_IMG_WH, bbox_scale_factor=1.2, std=4):
+        self.infer = regressor if isinstance(regressor, InferenceRegressor) else InferenceRegressor(regressor, precision)
+        self.smpl = smpl
+        self.out_wh, self.bbox_scale_factor, self.std = int(out_wh), float(bbox_scale_factor), int(std)
+        self._identity = None
+
+    def refresh(self):
+        self.infer.refresh()
+        return self
+
+    def _identity_rotmats(self, B, device):
+        if self._identity is None or self._identity.shape[0] < B or self._identity.device != device:
+            eye = torch.eye(3, device=device, dtype=torch.float32).expand(B, 24, 3, 3).contiguous()
+            if torch.cuda.is_current_stream_capturing():
+                return eye                      # (memory of the capture's pool: not kept)
+            self._identity = eye
+        return self._identity[:B]
+
+    @hipabi.on_tensor_device
+    def __call__(self, silhouettes, joints2D, vis_wh=None):
+        """-> {'proxy_rep' [B,1+J,out,out], 'cam_wp' [B,3], 'pose' [B,144] (6-D), 'pose_rotmats' [B,24,3,3], 'shape' [B,10], 'vertices' [B,6890,3],
+        'joints' [B,90,3], 'vertices2D' [B,6890,2] in pixels of a vis_wh (default out_wh) square, 'reposed_vertices' [B,6890,3] (identity
+        rotations, the predicted shape), 'joints2D_cropped' [B,J,2], 'boxes' [B,6], 'valid' [B] bool}.  An invalid sample (see
+        create_proxy_representation_batch) gets the regressor's answer to an all-zero input; `valid` says which."""
+        with torch.no_grad():
+            proxy, jc, boxes = create_proxy_representation_batch(silhouettes, joints2D, self.out_wh, self.bbox_scale_factor, self.std)
+            cam, pose, shape, rot = self.infer(proxy, rotmats=True)
+            B = proxy.shape[0]
+            rot = rot.view(B, 24, 3, 3)
+            shape = shape.contiguous()
+            verts, joints = self.smpl.forward_arrays(shape, rot)
+            v2d = cam_utils.undo_keypoint_normalisation(cam_utils.orthographic_project_torch(verts, cam), vis_wh or self.out_wh)
+            reposed, _ = self.smpl.forward_arrays(shape, self._identity_rotmats(B, proxy.device), want_joints=False)
+        return {'proxy_rep': proxy, 'cam_wp': cam, 'pose': pose, 'pose_rotmats': rot, 'shape': shape, 'vertices': verts, 'joints': joints,
+                'vertices2D': v2d, 'reposed_vertices': reposed, 'joints2D_cropped': jc, 'boxes': boxes, 'valid': boxes[:, 4] != 0}
