@@ -11,7 +11,13 @@ still hold the sentinel, bit for bit, naming the first damaged byte offset relat
 with NaN, so an element the kernel should have written and did not is a NaN in the comparison that follows.
 
 `at_end_of_poison()` places an input so that its last byte is followed by a NaN margin (what test_dgrad_x3_with_fused_batchnorm_sums
-does by hand): a read past the operand's end becomes a NaN in the result.
+does by hand): a read past the operand's end becomes a NaN in the result.  2-byte element types (bf16 bit patterns as int16) get the bf16
+quiet-NaN pattern 0x7FC0 as margin.
+
+`planes_with_gaps()` re-homes a [3][ps] int16 plane operand (straps_split3_bf16[_cm], the weight packs) as [3][ps'] with ps' > n: split3 always
+gives ps == n rounded up to 8, so a read past plane 0 lands in plane 1 -- finite, plausible data.  Here every plane is followed by a gap of
+0x7FC0 words: an over-read whose value is USED is a NaN in the result.  `PlaneGuard` is the output counterpart (straps_conv_fwd_x3p's y_planes
+with y_plane_stride larger than the extent): margins as a Guard, and the gap words behind every plane must be unchanged after the call.
 
 The margins are ordinary memory of the test; nothing here provokes a fault.  No GPU kernels of its own: torch fills and compares.
 """
@@ -20,6 +26,8 @@ import torch
 MARGIN = 64 << 10                 # bytes on either side (the widest row stride of the guarded outputs, 6890 * 3 * 4 B, fits 0.79 times)
 ALIGN = 256                       # the body starts on a 256-byte boundary, as a tensor of the caching allocator would
 SENTINEL = 0x7FC0BEEF             # a quiet-NaN bit pattern with a payload, as int32: a stray READ of a margin is a NaN as well
+BF16_NAN = 0x7FC0                 # bf16 quiet NaN (as int16: 32704): the margin / gap word of 2-byte plane tensors
+PLANE_GAP = MARGIN // 2           # default gap behind a plane, in 2-byte elements (a 256-row tile of one 32-channel chunk is 8 192 elements)
 
 
 class Guard:
@@ -78,9 +86,46 @@ class Zone:
     def at_end(self, t):
         return at_end_of_poison(t, self.device)
 
+    def planes(self, planes, n, gap=PLANE_GAP):
+        return planes_with_gaps(planes, n, self.device, gap)
+
+    def guarded_planes(self, n, gap=PLANE_GAP, name=''):
+        """-> (int16 [3][ps'] output planes with guarded gaps, ps'); checked by check()"""
+        g = PlaneGuard(n, self.device, gap, name or 'planes %d' % len(self.guards))
+        self.guards.append(g)
+        return g.view, g.ps
+
     def check(self):
         for g in self.guards:
             g.check()
+
+
+class PlaneGuard(Guard):
+    """a guarded OUTPUT plane tensor: `.view` is int16 [3][ps], ps = n rounded up to 8 + gap; elements [n, ps) of every plane (the gap) and the
+    margins around the whole tensor must be unchanged after the call; the extents [0, n) are pre-filled with 0x7FC0 as well (an element the kernel
+    should have written and did not reads as NaN)."""
+
+    def __init__(self, n, device='cpu', gap=PLANE_GAP, name=''):
+        assert gap > 0 and gap % 8 == 0
+        self.n, self.ps = int(n), (int(n) + 7) // 8 * 8 + gap
+        Guard.__init__(self, (3, self.ps), torch.int16, device, fill=BF16_NAN, name=name)
+        assert self.view.data_ptr() % 16 == 0
+
+    def gap_damage(self):
+        """-> None, or (plane, element offset inside the plane, word found) of the first changed gap word."""
+        if self.base.is_cuda:
+            torch.cuda.synchronize(self.base.device)
+        bad = (self.view[:, self.n:] != BF16_NAN).nonzero()
+        if bad.numel():
+            pl, off = int(bad[0, 0]), int(bad[0, 1]) + self.n
+            return pl, off, int(self.view[pl, off]) & 0xFFFF
+        return None
+
+    def check(self):
+        Guard.check(self)
+        d = self.gap_damage()
+        assert d is None, ('plane gap %r (3 planes of %d elements at stride %d): the gap behind plane %d was overwritten at element %d of the plane '
+                           '(%d elements past its extent), found 0x%04x' % (self.name, self.n, self.ps, d[0], d[1], d[1] - self.n, d[2]))
 
 
 _LIVE = []
@@ -106,11 +151,33 @@ def at_end_of_poison(t, device=None, margin=MARGIN):
         return None
     device = t.device if device is None else device
     t = t.contiguous()
-    assert t.element_size() == 4, 'at_end_of_poison: 4-byte element types only'
+    assert t.element_size() in (2, 4), 'at_end_of_poison: 2- and 4-byte element types only'
     n = t.numel()
+    if t.element_size() == 2:
+        front = ALIGN // 2
+        base = torch.full((front + n + margin // 2,), BF16_NAN, dtype=torch.int16, device=device)
+        out = base[front:front + n].view(t.dtype).view(t.shape)
+        out.copy_(t)
+        return out
     front = ALIGN // 4
     base = torch.full((front + n + margin // 4,), float('nan'), dtype=torch.float32, device=device)
     body = base[front:front + n]
     out = body.view(t.dtype).view(t.shape) if t.dtype != torch.float32 else body.view(t.shape)
     out.copy_(t)
     return out
+
+
+def planes_with_gaps(planes, n, device=None, gap=PLANE_GAP):
+    """[3][ps] int16 planes whose first n elements each are the operand -> (copy [3][ps'], ps') with ps' = n rounded up to 8 + gap > n,
+    ps' % 8 == 0, a 16-byte-aligned base, and 0x7FC0 in every element outside the three extents: directly behind element n - 1 of every plane
+    (the gap; behind the last plane it is the margin) and in front of plane 0."""
+    assert planes.dim() == 2 and planes.shape[0] == 3 and planes.element_size() == 2 and planes.shape[1] >= n
+    assert gap > 0 and gap % 8 == 0
+    device = planes.device if device is None else device
+    ps = (n + 7) // 8 * 8 + gap
+    front = ALIGN // 2
+    base = torch.full((front + 3 * ps,), BF16_NAN, dtype=torch.int16, device=device)
+    out = base[front:].view(3, ps)
+    out[:, :n].copy_(planes[:, :n])
+    assert out.data_ptr() % 16 == 0
+    return out, ps

@@ -1,0 +1,245 @@
+"""CPU: tests/conv_cases.py -- the Python restatement of the convolution family's dispatch -- held to everything the built library reveals without a
+launch (block counts, workspace bytes, route queries; no compute calls -- there is no GPU here), the conditions the case tables of
+tests/test_gpu_conv_edges.py are named for, and the coverage statement: the tables together reach every instantiation the product library can
+dispatch to.  A later change of a size rule that moves a case off its kernel fails here instead of thinning the coverage quietly."""
+import itertools
+
+import pytest
+
+import conv_cases as K
+from straps_amd import hipabi
+
+
+@pytest.fixture(scope='module')
+def lib():
+    hipabi.build()
+    return hipabi.load()
+
+
+def _conv_cases():
+    return K.FWD_EXPLICIT + K.FWD_AUTO + K.FWD_PLANES + K.DGRAD_EXPLICIT + K.DGRAD_S2_SMALL + K.DGRAD_AUTO
+
+
+def test_plane_route_block_counts_agree_for_every_case(lib):
+    """straps_conv_x3_stat_blocks / straps_conv_dgrad_x3_bn_blocks == the restatement, for every case under its own tile_cfg, under the twin's
+    (the named tile / the shared-epilogue bit) and under the A/B bits"""
+    n = 0
+    for (B, H, W, ci, co, k, s, cfg) in _conv_cases():
+        pad = K.pad_of(k)
+        twins = {cfg, cfg | 256, cfg | 512, cfg | 512 | 1024, cfg | K.SHARED_EPILOGUE_BIT}
+        p = K.fwd_problem(B, H, W, ci, co, k, s, pad)
+        twins.add(K.x3_route(p, cfg, {'y', 'stats'})[0][1] if K.x3_route(p, cfg, {'y', 'stats'})[0][0] == 'x3' else cfg)
+        for t in twins:
+            assert lib.straps_conv_x3_stat_blocks(B, H, W, ci, co, k, k, s, pad, t) == K.x3_stat_blocks(B, H, W, ci, co, k, s, pad, t), (B, H, W, ci, co, k, s, t)
+            if ci % 64 == 0 and co % 32 == 0:
+                assert lib.straps_conv_dgrad_x3_bn_blocks(B, H, W, ci, co, k, k, s, pad, t) == K.dgrad_x3_bn_blocks(B, H, W, ci, co, k, s, pad, t), \
+                    (B, H, W, ci, co, k, s, t)
+            n += 1
+    assert n > 1000
+
+
+def test_plane_route_block_counts_agree_on_a_grid(lib):
+    """the same over a grid of geometries around every threshold of the rules (128 / 256 / 512 tile equivalents, M % 128, halo slot limits)"""
+    maps = [(1, 1, 1), (1, 3, 43), (2, 8, 8), (4, 4, 8), (1, 4, 64), (8, 16, 16), (4, 32, 32), (2, 64, 64), (1, 128, 127), (1, 128, 128), (1, 129, 128), (2, 128, 128),
+            (2, 129, 128), (4, 128, 128), (4, 128, 129), (8, 128, 128), (1, 255, 257), (3, 91, 241), (16, 64, 64), (64, 16, 16), (128, 8, 8), (512, 8, 8), (32, 32, 32)]
+    for (B, H, W), (ci, co), (k, s), cfg in itertools.product(maps, ((64, 64), (64, 128), (128, 64), (256, 256), (128, 512)), ((3, 1), (3, 2), (1, 1), (1, 2)),
+                                                            (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 256, 512, 1536, 64)):
+        pad = K.pad_of(k)
+        assert lib.straps_conv_x3_stat_blocks(B, H, W, ci, co, k, k, s, pad, cfg) == K.x3_stat_blocks(B, H, W, ci, co, k, s, pad, cfg), (B, H, W, ci, co, k, s, cfg)
+        assert lib.straps_conv_dgrad_x3_bn_blocks(B, H, W, ci, co, k, k, s, pad, cfg) == K.dgrad_x3_bn_blocks(B, H, W, ci, co, k, s, pad, cfg), (B, H, W, ci, co, k, s, cfg)
+        if k == 1:
+            for c5 in (0, 1, 2, 5):
+                assert lib.straps_conv_x3f_stat_blocks(B, H, W, ci, co, 1, 1, s, 0, c5) == K.x3f_stat_blocks(B, H, W, ci, co, 1, s, 0, c5), (B, H, W, ci, co, s, c5)
+                assert lib.straps_conv_dgrad_x3f_bn_blocks(B, H, W, ci, co, 1, 1, s, 0, c5) == K.dgrad_x3f_bn_blocks(B, H, W, ci, co, 1, s, 0, c5), (B, H, W, ci, co, s, c5)
+    assert lib.straps_conv_x3f_stat_blocks(1, 8, 8, 64, 64, 3, 3, 1, 1, 0) == K.x3f_stat_blocks(1, 8, 8, 64, 64, 3, 1, 1, 0) == -1
+
+
+def test_fp32_operand_route_queries_agree_for_every_case(lib):
+    for (B, H, W, ci, co, s, cfg) in K.X3F_FWD:
+        assert lib.straps_conv_x3f_supported(ci, co, 1, 1, s, 0) == K.x3f_supported(ci, co, 1, s, 0) == 1
+        for t in (cfg, 0, 1, 2, 5):
+            assert lib.straps_conv_x3f_stat_blocks(B, H, W, ci, co, 1, 1, s, 0, t) == K.x3f_stat_blocks(B, H, W, ci, co, 1, s, 0, t), (B, H, W, ci, co, s, t)
+    for (B, H, W, ci, co, s, cfg) in K.X3F_DGRAD:
+        assert lib.straps_conv_x3f_supported(ci, co, 1, 1, s, 0) == 1
+        for t in (cfg, 0, 1, 2, 5):
+            assert lib.straps_conv_dgrad_x3f_bn_blocks(B, H, W, ci, co, 1, 1, s, 0, t) == K.dgrad_x3f_bn_blocks(B, H, W, ci, co, 1, s, 0, t), (B, H, W, ci, co, s, t)
+    for ci, co, k, s, pad in itertools.product((32, 64, 96, 128), (32, 64, 192), (1, 3), (1, 2, 3), (0, 1)):
+        assert lib.straps_conv_x3f_supported(ci, co, k, k, s, pad) == K.x3f_supported(ci, co, k, s, pad)
+
+
+def _wgrad_geometries():
+    grid = [(B, H, W, ci, co, k, s) for (B, H, W) in ((1, 1, 1), (1, 4, 8), (3, 2, 16), (5, 6, 32), (7, 2, 64), (2, 10, 24), (1, 91, 91), (2, 128, 128), (3, 20, 20), (64, 16, 16))
+            for (ci, co) in ((64, 64), (64, 128), (128, 64), (128, 256), (256, 128), (192, 128), (512, 512)) for (k, s) in ((3, 1), (3, 2), (1, 1), (1, 2))]
+    return K.WGRAD_HALO + K.WGRAD_TAP + K.WGRAD_F32 + grid
+
+
+def test_weight_gradient_queries_agree_and_every_plan_stays_inside_the_advertised_workspace(lib):
+    """straps_conv_wgrad_workspace_bytes is the fp32 plan's size.  The kernels on the planes choose their own blocks, splits and chunk size: their
+    partials -- splits x Cout x taps x Cin floats, every split written, the reduction reads exactly `splits` of them -- must fit."""
+    for c in _wgrad_geometries():
+        B, H, W, ci, co, k, s = c
+        pad = K.pad_of(k)
+        adv = lib.straps_conv_wgrad_workspace_bytes(B, H, W, ci, co, k, k, s, pad)
+        assert adv == K.wgrad_workspace_bytes(B, H, W, ci, co, k, s, pad), c
+        assert lib.straps_conv_wgrad_x3_on_planes(B, H, W, ci, co, k, k, s, pad) == int(K.wgrad_x3_route(B, H, W, ci, co, k, s, pad) != 0), c
+        for planes in (True, False):
+            pl = K.wgrad_plan(B, H, W, ci, co, k, s, pad, planes)
+            assert 1 <= pl.splits and pl.splits * co * pl.taps * ci * 4 <= adv, (c, pl)
+            assert pl.splits * pl.unit >= pl.units, (c, pl)          # the splits cover every pixel / chunk
+    for (B, H, W, ci, co, s, bn) in K.WGRAD_X3F + [(b, h, w, ci, co, s, 0) for (b, h, w, ci, co, k, s) in _wgrad_geometries() if k == 1]:
+        pl = K.wgrad_x3f_plan(B, H, W, ci, co, s, bn)
+        assert lib.straps_conv_wgrad_x3f_workspace_bytes(B, H, W, ci, co, 1, 1, s, 0) == K.wgrad_x3f_workspace_bytes(B, H, W, ci, co, 1, s, 0) \
+            == pl.splits * co * ci * 4, (B, H, W, ci, co, s)
+        assert pl.splits * pl.unit >= pl.units
+    assert lib.straps_conv_wgrad_x3f_workspace_bytes(1, 8, 8, 64, 64, 3, 3, 1, 1) == K.wgrad_x3f_workspace_bytes(1, 8, 8, 64, 64, 3, 1, 1) == 0
+
+
+def test_the_tables_reach_every_instantiation_the_product_library_dispatches_to():
+    got = K.reached()
+    missing = [i for i in K.REQUIRED if i not in got and i not in K.UNREACHABLE]
+    assert not missing, 'no case reaches %s' % missing
+    assert all(i in K.REQUIRED or i[0] == 'wgrad_x3' for i in K.UNREACHABLE)
+    assert not [i for i in K.UNREACHABLE if i in got], 'listed as unreachable, but a case reaches it'
+    assert not [i for i in got if i not in K.REQUIRED], 'an instantiation the coverage statement does not know'
+    # what the issue names, spelled out: dispatch_x3_abl<0> cases 1-5 and 7-12, the three launch_x3h forms, every dispatch_lean form with EPI 1 and 2
+    # (tile 9 excepted: unreachable), every x3f tile configuration, every weight-gradient block
+    for cfg in (1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12):
+        assert ('x3', cfg, 0) in got
+    for cfg, epi in itertools.product((3, 5, 7, 11, 12), (1, 2)):
+        assert ('x3', cfg, epi) in got
+    for epi in (0, 1, 2):
+        assert ('x3h', 1, epi) in got and ('x3h', 3, epi) in got
+    assert ('x3h', 2, 0) in got
+
+
+def test_unreachable_instantiations_stay_unreachable_over_a_sweep():
+    """lean tile 9: the rule picks tile 9 only for several one-tap classes, i.e. a 1x1 / stride-2 gradient, whose dead classes take the shared epilogue"""
+    for (B, H, W), (ci, co), (k, s) in itertools.product(((1, 1, 1), (1, 1, 2), (2, 9, 14), (1, 255, 257), (2, 255, 257), (1, 512, 512), (4, 256, 256)),
+                                                        ((128, 32), (256, 32), (512, 64), (1024, 64)), ((3, 1), (3, 2), (1, 1), (1, 2))):
+        for kind, ops in [('fwd', K.fwd_ops('raw_stats'))] + [('dgrad', o) for o in K.DGRAD_FORMS.values()]:
+            p = (K.fwd_problem(B, H, W, co, ci, k, s, K.pad_of(k)) if kind == 'fwd' else K.dgrad_problem(B, H, W, ci, co, k, s, K.pad_of(k)))
+            inst = K.x3_route(p, 0, ops)[0]
+            assert not (inst[:2] == ('x3', 9) and inst[2] != 0), (kind, B, H, W, ci, co, k, s, ops)
+    for c in _wgrad_geometries():
+        assert K.wgrad_plan(*c, K.pad_of(c[5])).inst not in K.UNREACHABLE
+
+
+def test_explicit_tile_tables_hold_the_rows_they_are_named_for():
+    for table, kind in ((K.FWD_EXPLICIT, 'fwd'), (K.DGRAD_EXPLICIT, 'dgrad')):
+        seen = {}
+        for (B, H, W, ci, co, k, s, cfg) in table:
+            p = (K.fwd_problem if kind == 'fwd' else K.dgrad_problem)(B, H, W, ci, co, k, s, K.pad_of(k))
+            inst, bm, _ = K.x3_route(p, cfg, {'y', 'stats'} if kind == 'fwd' else K.DGRAD_FORMS['addend'])
+            assert inst == ('x3', cfg, 0) and bm == K.X3_BM[cfg]
+            red = ci if kind == 'fwd' else co
+            seen.setdefault((cfg, k, s, red), set()).add(max(x.M for x in p.cls))
+        assert set(seen) == {(cfg, k, s, r) for cfg in K.X3_TILES for (k, s, r) in K.VARIANTS}
+        for (cfg, k, s, r), ms in seen.items():
+            bm = K.X3_BM[cfg]
+            assert bm + 1 in ms and 2 * bm - 1 in ms and any(m < bm // 2 for m in ms), (cfg, ms)
+    # H = 1 and W = 1 maps under a 3x3 / pad 1 filter at every row tile
+    for bm, maps in K.EDGE_MAPS.items():
+        assert any(h == 1 for _, h, w in maps) and any(w == 1 for _, h, w in maps), bm
+
+
+def test_automatic_rule_tables_hold_the_classes_they_are_named_for():
+    def fwd(c, form='raw_stats'):
+        B, H, W, ci, co, k, s, cfg = c
+        return K.x3_route(K.fwd_problem(B, H, W, ci, co, k, s, K.pad_of(k)), cfg, K.fwd_ops(form))
+    want = [('x3', 7, 1)] * 2 + [('x3', 5, 1)] * 2 + [('x3', 12, 1)] * 2 + [('x3', 3, 1), ('x3', 7, 1)] + [('x3h', 1, 1)] * 2 + [('x3', 11, 1)] * 4 + [('x3h', 3, 1)] * 4 + \
+           [('x3h', 2, 0)] * 2 + [('x3h', 1, 1)]
+    assert [fwd(c)[0] for c in K.FWD_AUTO] == want
+    assert [fwd(c, 'fused')[0] for c in K.FWD_AUTO] == [(a, b, 0) for (a, b, _) in want]
+    # one row short of and one row past a multiple of the tile, in every size class of the 128-channel rule
+    for short, past in ((0, 1), (2, 3), (4, 5)):
+        bm = fwd(K.FWD_AUTO[short])[1]
+        ms, mp = (K.FWD_AUTO[i][0] * K.FWD_AUTO[i][1] * K.FWD_AUTO[i][2] for i in (short, past))
+        assert ms % bm == bm - 1 and mp % bm == 1
+    # gradients: the lean form with an addend, bits and fused sums; the fp32-mask sums on the shared epilogue of the SAME tile
+    for c in K.DGRAD_AUTO:
+        B, H, W, ci, co, k, s, cfg = c
+        p = K.dgrad_problem(B, H, W, ci, co, k, s, K.pad_of(k))
+        r = {n: K.x3_route(p, cfg, o)[0] for n, o in K.DGRAD_FORMS.items()}
+        if (k, s) == (1, 2):
+            assert set(r.values()) == {('x3', 9, 0)}
+            continue
+        assert r['addend'][2] == r['bits'][2] == r['bn_mask'][2] == r['bn_bits'][2] == 2 and r['bn_out'] == r['addend'][:2] + (0,)
+        assert K.x3_route(p, K.twin_cfg(p, cfg, K.DGRAD_FORMS['addend']), K.DGRAD_FORMS['addend'])[0] == r['addend'][:2] + (0,)
+    got = [K.x3_route(K.dgrad_problem(*c[:7], K.pad_of(c[5])), 0, K.DGRAD_FORMS['addend'])[0][:2] for c in K.DGRAD_AUTO]
+    assert got == [('x3', 7), ('x3', 5), ('x3', 12), ('x3h', 1), ('x3h', 3), ('x3h', 3), ('x3', 11), ('x3', 3), ('x3', 3), ('x3', 11), ('x3', 12), ('x3', 9), ('x3', 12)]
+    # every stride-2 case has a ragged class
+    for c in K.DGRAD_AUTO:
+        if c[6] == 2:
+            p = K.dgrad_problem(*c[:7], K.pad_of(c[5]))
+            bm = K.x3_route(p, 0, K.DGRAD_FORMS['addend'])[1]
+            assert len(p.cls) == 4 and any(x.M % bm for x in p.cls)
+
+
+def test_stride_two_small_maps_have_one_two_and_four_classes_and_dead_ones():
+    n = {}
+    for c in K.DGRAD_S2_SMALL:
+        B, H, W, ci, co, k, s, cfg = c
+        p = K.dgrad_problem(B, H, W, ci, co, k, s, K.pad_of(k))
+        n.setdefault(k, set()).add(len(p.cls))
+        if k == 1:
+            assert [x.ntaps for x in p.cls] == [1] + [0] * (len(p.cls) - 1)
+        else:
+            assert all(x.ntaps > 0 for x in p.cls)
+    assert n == {1: {1, 2, 4}, 3: {1, 2, 4}}
+
+
+def test_fp32_operand_tables_hold_the_streaming_conditions():
+    fewer, one_more, by_rule = set(), set(), set()
+    for table, prob, ops in ((K.X3F_FWD, K.fwd_problem, {'y', 'stats'}), (K.X3F_DGRAD, K.dgrad_problem, {'y', 'res', 'res_bits', 'bnr_raw'})):
+        for (B, H, W, ci, co, s, cfg) in table:
+            p = prob(B, H, W, ci, co, 1, s, 0)
+            inst = K.x3f_route(p, cfg, ops)[0]
+            if inst[0] != 'x3f_stream':
+                continue
+            wgs, mt = K.stream_workgroups(p, inst[1])
+            full = max(1, min(2, (160 * 1024) // K.stream_lds_bytes(64 if inst[1] == 256 else 128, inst[1], 2, inst[1] == 256, p.Cin)) * 256 // (p.Cout // inst[1]))
+            if mt < full:
+                fewer.add((table is K.X3F_FWD, inst[1]))
+            if mt > full and mt % full == 1:
+                one_more.add((table is K.X3F_FWD, inst[1]))
+            if cfg == 0:
+                by_rule.add(table is K.X3F_FWD)
+    assert fewer == {(f, bn) for f in (True, False) for bn in (256, 128, 64)}
+    assert one_more == {(f, bn) for f in (True, False) for bn in (256, 128, 64)}
+    assert by_rule == {True, False}
+
+
+def test_weight_gradient_tables_hold_the_plans_they_are_named_for():
+    plans = {c: K.wgrad_plan(*c, 1) for c in K.WGRAD_HALO}
+    assert plans[(1, 4, 8, 64, 64, 3, 1)] == K.WPlan(('wgrad3_x3', 32), 1, 1, 1, 1, 9)                     # one chunk, one split
+    assert {c[2] for c in K.WGRAD_HALO} == {8, 16, 32, 64}
+    for w in (8, 16, 32, 64):
+        assert {plans[c].inst[1] for c in K.WGRAD_HALO if c[2] == w} >= ({32, 64} if w < 64 else {32, 64})
+    assert any(p.units % p.unit for p in plans.values() if p.inst[1] == 32) and any(p.units % p.unit for p in plans.values() if p.inst[1] == 64)
+    # the 64-pixel plan is refused by the row count only: it has half the chunks of the 32-pixel plan, and half the chunks never need more splits
+    for B, H, W, (ci, co) in itertools.product(range(1, 30), range(1, 13), (8, 16, 32, 64), ((64, 64), (128, 256), (384, 1024), (512, 1024))):
+        p32, p64 = K.wgrad3_plan(B, H, W, ci, co, 3, 1, 1), K.wgrad3_plan(B, H, W, ci, co, 3, 1, 1, 64)
+        if p32 and p64:
+            assert p64[0] * 2 == p32[0] and p64[2] <= p32[2], (B, H, W, ci, co)
+    # per-tap kernel: every block at M in {1, 31, 33, 129} where its rule admits them, a short / an empty last split, each bound of the split count
+    by_block = {}
+    for c in K.WGRAD_TAP:
+        pl = K.wgrad_plan(*c, K.pad_of(c[5]))
+        assert pl.inst[0] == 'wgrad_x3', c
+        d = by_block.setdefault(pl.inst[1:], dict(M=set(), last=set(), clamp=set()))
+        d['M'].add(pl.units); d['last'].add(K.last_split_state(pl)); d['clamp'].add(K.wgrad_clamp(*c, K.pad_of(c[5])))
+    assert set(by_block) == {(256, 128), (128, 64), (64, 128), (128, 128), (64, 64)}
+    for blk, d in by_block.items():
+        if blk != (128, 128):                                   # (128 x 128: 1x1 layers from 8 192 pixels on only)
+            assert {1, 31, 33, 129} <= d['M'], (blk, d['M'])
+        assert {'short', 'empty'} <= d['last'], (blk, d['last'])
+        assert {'max_s', 'target'} <= d['clamp'], (blk, d['clamp'])
+    assert 'cap' in by_block[(256, 128)]['clamp']                # (the only block whose target exceeds the fp32 plan's count)
+    # fp32-operand weight gradient: every block with and without the operand-path BatchNorm, at the four small pixel counts
+    fb = {}
+    for c in K.WGRAD_X3F:
+        pl = K.wgrad_x3f_plan(*c)
+        fb.setdefault(pl.inst[1:3], set()).add(pl.units)
+    assert set(fb) == {(256, 64), (64, 256), (256, 128), (128, 256), (128, 128), (64, 64)} and all({1, 31, 33, 129} <= m for m in fb.values())
+    assert 'empty' in {K.last_split_state(K.wgrad_x3f_plan(*c)) for c in K.WGRAD_X3F}
+    assert {K.wgrad_plan(*c, K.pad_of(c[5]), planes=False).inst for c in K.WGRAD_F32} == {('wgrad3_f32',), ('wgrad_f32', 64), ('wgrad_f32', 128)}
