@@ -786,6 +786,41 @@ int straps_predict_proxy_input(const uint8_t* sil, const float* joints2d, int ld
  * (6890 vertices -> PVE / PVE-SC / PVE-PA sums, 14 joints -> MPJPE / -SC / -PA sums).                */
 int straps_point_metrics(const float* pred, const float* target, float* out3, long long batch,
                          int npoints, void* stream);
+/* ---- on-device evaluation (metrics/eval_metrics_tracker.py; csrc/metrics.hip, csrc/eval.hip; added without a version change) ----
+ * Every entry below checks its arguments before any HIP call (STRAPS_EINVAL, straps_last_error() names the argument), launches on
+ * `stream`, allocates nothing and never synchronises, so it can be captured into a hipGraph.
+ *
+ * straps_point_align: straps_point_metrics (same kernel, out3 bit-identical) that also writes the transformed predictions, the
+ * `return_transformed_points` arrays of update_per_batch: pred_sc [B][npoints][3] = (x - mu1) * (rms2 / rms1) + mu2
+ * (scale_and_translation_transform_batch, utils/eval_utils.py:66-85) and pred_pa [B][npoints][3] = s R x + t
+ * (compute_similarity_transform, :7-55, det R = +1), each coordinate computed in fp64 and rounded once to fp32.  Each of out3,
+ * pred_sc, pred_pa may be NULL (not computed / not written); at least one must be non-NULL.  npoints >= 3.
+ * The rotation is built from the two leading singular pairs of the 3x3 cross-covariance K (eigenvectors of K^T K in fp64) and their
+ * cross products.  The eigenvectors lose about (sigma1 / sigma2)^2 of fp64's precision, so the result stays within one fp32 ulp of
+ * the reference's SVD route while sigma2 / sigma1 >= 5e-5 (asserted on a numpy emulation of the kernel, tests/test_eval_cases_cpu.py)
+ * and degrades quadratically below that; towards collinear points (sigma2 -> 0) the reference's answer becomes arbitrary as well.
+ * npoints = 3 is no special case: three
+ * centred points give a rank-2 K (sigma3 = 0), and the construction never uses sigma3 (tests/test_eval_cases_cpu.py).             */
+int straps_point_align(const float* pred, const float* target, float* out3, float* pred_sc,
+                       float* pred_pa, long long batch, int npoints, void* stream);
+/* Confusion counts of two byte masks per frame (eval_metrics_tracker.py:158-178): pred, target [B][npix] uint8, any non-zero byte
+ * is foreground; counts4 [B][4] int32 = { true positives, false positives, true negatives, false negatives }.  Integer arithmetic
+ * only: the result is exact and independent of any order, and of what counts4 held before the call.  1 <= npix < 2^31.            */
+int straps_silhouette_counts(const uint8_t* pred, const uint8_t* target, int32_t* counts4,
+                             long long batch, long long npix, void* stream);
+/* Silhouette of a mesh under the weak-perspective camera cam_wp [B][3] = (s, tx, ty) the regressor predicts.
+ *   projection, per vertex, fp32, unfused: u = s * (x + tx), v = s * (y + ty)   (utils/cam_utils.py:21-22)
+ *   mask [B][wh][wh] uint8: mask[b][r][c] = 1 iff the pixel-centre sample ((2c + 1 - wh) / wh, (2r + 1 - wh) / wh) lies inside the
+ *   projection of some face, else 0.  Rows run with +v, no flip: the pixel grid of undo_keypoint_normalisation
+ *   (utils/joints2d_utils.py:5-10), on which (u + 1) * wh / 2 is a pixel coordinate.
+ *   coverage rule of straps_rasterize_parts: with the edge function e(a, b, p) = (px - ax) * (by - ay) - (py - ay) * (bx - ax), a
+ *   sample is inside when e(v1,v2,p), e(v2,v0,p), e(v0,v1,p) are all >= 0 or all <= 0 (two-sided, edges included); faces with
+ *   |e(v0,v1,v2)| <= 1e-12 (or NaN) and faces with a vertex index outside [0, nverts) are skipped.  No depth test.
+ * verts [B][nverts][3], faces [nfaces][3]; workspace: straps_wp_silhouette_workspace_bytes(batch, nverts) =
+ * batch * nverts * 2 * sizeof(float) bytes (the projected vertices), 4-byte aligned.  1 <= wh <= 4096.  Deterministic.             */
+size_t straps_wp_silhouette_workspace_bytes(long long batch, int nverts);
+int straps_wp_silhouette(const float* verts, const int32_t* faces, const float* cam_wp, uint8_t* mask,
+                         void* workspace, long long batch, int nverts, int nfaces, int wh, void* stream);
 /* torch.optim.Adam defaults (run_train.py:200-201) over one flat fp32 buffer:
  * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps);
  * grad_scale multiplies g first (1/world_size after a sum all-reduce).  step_dev (optional device

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
-           'regressor.hip', 'regressor_train.hip', 'predict.hip']
+           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -271,6 +271,11 @@ SIGNATURES = {
     'straps_crop_resize': (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _P, _P, _P, _I, _I, _I, _I, _P]),
     # predict-side front end: silhouettes + keypoints -> proxy input (csrc/predict.hip; added without a version change)
     'straps_predict_proxy_input': (_I, [_P, _P, _I, _P, _I, _D, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    # on-device evaluation: aligned points, silhouette counts, weak-perspective silhouette (csrc/metrics.hip, csrc/eval.hip; added without a version change)
+    'straps_point_align': (_I, [_P, _P, _P, _P, _P, _L, _I, _P]),
+    'straps_silhouette_counts': (_I, [_P, _P, _P, _L, _L, _P]),
+    'straps_wp_silhouette_workspace_bytes': (_Z, [_L, _I]),
+    'straps_wp_silhouette': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     'straps_comm_unique_id': (_I, [_P]),
     'straps_comm_init_rank': (_I, [_P, _I, _I, C.POINTER(C.c_void_p)]),
     'straps_comm_destroy': (_I, [_P]),

@@ -98,3 +98,49 @@ class NMRRenderer(nn.Module):
     def forward(self, vertices, cam_ts):
         """vertices (B, N, 3), cam_ts (B, 1, 3) or (B, 3) -> (B, wh, wh) long part ids (renderers/nmr_renderer.py:76-91)."""
         return self.render_arrays(vertices, cam_ts).long()
+
+
+class WeakPerspectiveSilhouetteRenderer(nn.Module):
+    """Predicted silhouette for evaluation: the mesh under the weak-perspective camera [s, tx, ty] the regressor predicts, as a byte mask
+    (csrc/eval.hip, straps_wp_silhouette).  mask[b, r, c] = 1 iff the pixel centre ((2c + 1 - wh) / wh, (2r + 1 - wh) / wh) lies inside
+    the projection u = s (x + tx), v = s (y + ty) of some face; rows run with +v (no flip), the pixel grid of
+    undo_keypoint_normalisation, so the mask lines up with Predictor's `vertices2D`.
+
+        renderer = WeakPerspectiveSilhouetteRenderer(faces, img_wh=256).to(device)
+        silhouettes = renderer(out['vertices'], out['cam_wp'])          # uint8 [B, wh, wh]
+
+    faces=None loads config.SMPL_FACES_PATH, as NMRRenderer does."""
+
+    def __init__(self, faces=None, img_wh=256):
+        super().__init__()
+        if faces is None:
+            if not os.path.isfile(config.SMPL_FACES_PATH):
+                raise RuntimeError('WeakPerspectiveSilhouetteRenderer: %s not found; pass faces= (e.g. from synthetic_smpl_model())' % config.SMPL_FACES_PATH)
+            faces = np.load(config.SMPL_FACES_PATH)
+        if isinstance(faces, torch.Tensor):
+            faces = faces.detach().cpu().numpy()
+        faces = np.ascontiguousarray(np.asarray(faces).astype(np.int32))
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+            raise RuntimeError('WeakPerspectiveSilhouetteRenderer: faces must be [F,3] (got %s)' % (faces.shape,))
+        if not 1 <= int(img_wh) <= 4096:
+            raise RuntimeError('WeakPerspectiveSilhouetteRenderer: img_wh must be in 1..4096 (got %r)' % (img_wh,))
+        self.register_buffer('faces', torch.from_numpy(faces))
+        self.img_wh = int(img_wh)
+
+    @hipabi.on_tensor_device
+    def forward(self, vertices, cam_wp):
+        """vertices [B,N,3], cam_wp [B,3] (fp32 GPU) -> uint8 [B,wh,wh], 1 = covered."""
+        hipabi.require_gpu_tensor(vertices, 'vertices', torch.float32)
+        hipabi.require_gpu_tensor(cam_wp, 'cam_wp', torch.float32)
+        hipabi.require_gpu_tensor(self.faces, 'WeakPerspectiveSilhouetteRenderer buffers (call .to(device))', torch.int32)
+        if vertices.dim() != 3 or vertices.shape[2] != 3 or tuple(cam_wp.shape) != (vertices.shape[0], 3):
+            raise RuntimeError('WeakPerspectiveSilhouetteRenderer: expected vertices [B,N,3] and cam_wp [B,3], got %s and %s'
+                               % (tuple(vertices.shape), tuple(cam_wp.shape)))
+        B, N, wh = vertices.shape[0], vertices.shape[1], self.img_wh
+        vertices, cam_wp = vertices.detach().contiguous(), cam_wp.detach().contiguous()
+        L = hipabi.lib()
+        out = torch.empty(B, wh, wh, device=vertices.device, dtype=torch.uint8)
+        ws = torch.empty(L.straps_wp_silhouette_workspace_bytes(B, N) // 4, device=vertices.device, dtype=torch.float32)
+        hipabi.check(L.straps_wp_silhouette(hipabi.ptr(vertices), hipabi.ptr(self.faces), hipabi.ptr(cam_wp), hipabi.ptr(out), hipabi.ptr(ws),
+                                            B, N, self.faces.shape[0], wh, hipabi.stream_ptr()), 'straps_wp_silhouette')
+        return out
