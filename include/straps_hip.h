@@ -933,6 +933,56 @@ int straps_comm_size(void* comm);
 const char* straps_comm_library(void);
 int straps_allreduce_grads(float* flat_g, long long n, void* comm, void* stream);
 
+/* ---- test-time fitting of cam, 6-D pose and shape to 2-D keypoints (csrc/fit.hip; added without a version change) ----------------
+ * The reference stops at the regressor's answer (predict/predict_3D.py:116-149); this is the optimisation users of an HMR-family
+ * regressor run after it, as ONE kernel launch that holds all iterations: one wave per body, parameters and Adam moments in registers.
+ *
+ * A body's row est[157] is the regressor's: cam = [s, tx, ty] | x6[144] | beta[10].  With a prior centre est0[157]:
+ *   R_j  = Gram-Schmidt of x6[6j..6j+5], exactly straps_rot6d_fwd (interleaved layout, 1e-12 clamps);
+ *   X_k  = kinematic posed joint kp_src[k] (0..23), or tracked mesh vertex kp_src[k] - 24 after the full LBS (template, shape
+ *          directions, pose correctives, dense skinning): the values straps_smpl_fwd writes to joints rows 0..23 / to its vertex rows;
+ *   p_k  = s (X_k.x + tx, X_k.y + ty);   that_k = 2 t_k / img_wh - 1 (t_k the pixel target);   r2_k = |p_k - that_k|^2;
+ *   w_k  = conf_k^2 when conf_k is finite and > 0 and t_k is finite, else 0 (the residual is then not evaluated); conf == NULL: all ones;
+ *   rho(r2) = sigma^2 r2 / (sigma^2 + r2) for robust_sigma > 0, else r2;
+ *   E    = sum_k w_k rho(r2_k) + lambda_pose |x6 - x6_0|^2 + lambda_shape |beta - beta_0|^2      (per body; no batch mean).
+ * g = dE/dest exactly.  Adam per element, the formula of straps_adam_step (bias corrections in double, b^t by squaring) with t = step0 + i + 1 and the learning rate of the
+ * element's block (lr_cam, lr_pose, lr_shape).  iters = n: evaluate (E_i, g_i) at est_i and update, i = 0..n-1, then evaluate once more
+ * at est_n (n + 1 evaluations, n updates; iters = 0 is a pure evaluation and leaves est and the moments bit-identical).  No early stop.
+ *   est         in: the start; out: est_n.                 est0: the prior centre; NULL = est as given; its cam columns are never used.
+ *   exp_avg(_sq) Adam moments, in/out; both NULL = start at zero, not stored.  A call split in two with the moments and step0 carried
+ *               over is bit-identical to the whole.
+ *   energy      [batch][iters + 1]: E_i of every evaluation, or NULL.      grad: g at the last evaluation, or NULL.
+ *   best_est / best_energy: the iterate of the smallest E_i (the first one; a NaN never replaces what is held), or NULL.
+ *   kp2d        [batch][n_kp][2]: p_k at the last evaluation, or NULL.
+ * vert_dirs rows are the blend directions of a tracked vertex in the column order of STRAPS_SMPL_KP (0 template, 1..10 shape,
+ * 11..217 pose correctives, 218..223 zero).  j_template, j_shapedirs, vert_dirs and vert_w must be 16-byte aligned.  Out-of-range
+ * entries of parents / kp_src are clamped into range on the device.  Results are bit-reproducible and a body's result depends on
+ * nothing but that body's inputs.  Arguments are checked before any HIP call; no workspace, no allocation, never synchronises.  */
+typedef struct {
+    const float* j_template;    /* [24][3], as straps_smpl_model_t                          */
+    const float* j_shapedirs;   /* [24][3][10]                                               */
+    const int32_t* parents;     /* [24]                                                      */
+    const float* vert_dirs;     /* [n_verts][3][224]: D[k] of the tracked vertex, k as STRAPS_SMPL_KP
+                                   (0 template, 1..10 shape, 11..217 pose, 218..223 zero)    */
+    const float* vert_w;        /* [n_verts][24] dense skinning weights                      */
+    const int32_t* kp_src;      /* [n_kp]: 0..23 kinematic joint, 24+i tracked vertex i      */
+    int32_t n_verts;            /* 0..16 */
+    int32_t n_kp;               /* 1..32 */
+} straps_fit_model_t;
+typedef struct {
+    int32_t iters, step0;       /* 0 <= iters <= 10000 */
+    float lr_cam, lr_pose, lr_shape, beta1, beta2, eps;
+    float robust_sigma, lambda_pose, lambda_shape, img_wh;
+} straps_fit_opts_t;
+int straps_fit_keypoints(const straps_fit_model_t* model, const straps_fit_opts_t* opts,
+        float* est /*[B][157] in/out*/, const float* est0 /*[B][157]; NULL = est as given*/,
+        const float* targets /*[B][n_kp][2] px*/, const float* conf /*[B][n_kp] or NULL*/,
+        float* exp_avg, float* exp_avg_sq /*[B][157] in/out; both NULL = start at zero, not stored*/,
+        float* energy /*[B][iters+1] or NULL*/, float* grad /*[B][157] at the last evaluation, or NULL*/,
+        float* best_est /*[B][157] or NULL*/, float* best_energy /*[B] or NULL*/,
+        float* kp2d /*[B][n_kp][2] normalised projection at the last evaluation, or NULL*/,
+        long long batch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

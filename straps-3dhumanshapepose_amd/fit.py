@@ -1,0 +1,198 @@
+"""Test-time fitting of the regressor's answer to the 2-D keypoints it was given (straps_fit_keypoints, csrc/fit.hip).
+
+The reference's predict path (predict/predict_3D.py:116-149) stops at the regressor; what it returns does not reproject onto the
+keypoints.  `KeypointFitter` runs a fixed number of Adam steps on (cam, 6-D pose, shape) against the reprojection error of the
+keypoints, with quadratic priors that hold pose and shape near the regressor's answer, as ONE kernel launch: one wave per body, all
+iterations inside the kernel.  Only the 24 kinematic joints and up to 16 tracked mesh vertices take part, so no mesh is built; the 45
+regressed joints (rows 45..89 of the 90-joint output) need the mesh and are refused.
+
+The defaults (100 iterations, lr 0.01, lambda 1e-3) are the values of a float64 experiment on the synthetic model of this package: nobody
+has tuned them on real detections, and neither a real SMPL model nor detector output was available when they were chosen.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import cam_utils, config, hipabi
+from .rigid_transform_utils import rot6d_to_rotmat
+
+NE, KP, MAX_KP, MAX_VERTS = 157, 224, 32, 16
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def pack_fit_model(smpl_or_model_dict, keypoints=None):
+    """-> dict of the tables of straps_fit_model_t: 'j_template' [24,3], 'j_shapedirs' [24,3,10], 'parents' [24] int32, 'vert_dirs'
+    [n_verts,3,224], 'vert_w' [n_verts,24], 'kp_src' [n_kp] int32, 'vertex_ids' [n_verts] (mesh ids of the tracked vertices, in order of
+    first appearance), 'n_verts', 'n_kp'.
+
+    keypoints (default config.ALL_JOINTS_TO_COCO_MAP): rows of the 90-joint output -- 0..23 kinematic joints, 24..44 the picked vertices
+    (`extra_vertex_ids`) -- or ('vertex', id) for any mesh vertex.  Rows 45..89 are regressed from the whole mesh: ValueError, as are more
+    than 32 keypoints or more than 16 distinct vertices.
+    For an SMPL module the rest-joint tables are the module's own buffers (the forward kernel's rest joints, on its device); for a model
+    dict they are computed as pack_smpl_model computes them.  Everything else is numpy."""
+    keypoints = list(config.ALL_JOINTS_TO_COCO_MAP if keypoints is None else keypoints)
+    is_module = isinstance(smpl_or_model_dict, torch.nn.Module)
+    if is_module:
+        s = smpl_or_model_dict
+        vt, sd, pd, W = _np(s.v_template), _np(s.shapedirs), _np(s.posedirs), _np(s.lbs_weights)
+        pick = _np(s._k_pick_ids)
+        jt, js, parents = s._k_j_template, s._k_j_shapedirs, s._k_parents
+    else:
+        m = smpl_or_model_dict
+        vt, sd, pd, W = (np.asarray(m[k], np.float32) for k in ('v_template', 'shapedirs', 'posedirs', 'weights'))
+        pick = np.asarray(m['extra_vertex_ids'], np.int64)
+        Jr = np.asarray(m['J_regressor'], np.float64)
+        jt = (Jr @ np.asarray(m['v_template'], np.float64)).astype(np.float32)                      # (as pack_smpl_model)
+        js = np.einsum('jv,vcl->jcl', Jr, np.asarray(m['shapedirs'], np.float64)).astype(np.float32)
+        parents = np.asarray(m['parents'], np.int32).copy()
+    nv_mesh = vt.shape[0]
+    if not 1 <= len(keypoints) <= MAX_KP:
+        raise ValueError('pack_fit_model: between 1 and %d keypoints (got %d)' % (MAX_KP, len(keypoints)))
+    vids, kp_src = [], []
+    for k in keypoints:
+        if isinstance(k, (tuple, list)):
+            if len(k) != 2 or k[0] != 'vertex' or not 0 <= int(k[1]) < nv_mesh:
+                raise ValueError("pack_fit_model: a keypoint is a row of the 90-joint output or ('vertex', id) with id in 0..%d (got %r)" % (nv_mesh - 1, k))
+            v = int(k[1])
+        else:
+            k = int(k)
+            if 0 <= k < 24:
+                kp_src.append(k)
+                continue
+            if not 24 <= k < 24 + len(pick):
+                raise ValueError('pack_fit_model: keypoint row %d is a joint regressed from the whole mesh (rows %d..89): it needs the mesh, '
+                                 'only rows 0..%d can be fitted' % (k, 24 + len(pick), 23 + len(pick)))
+            v = int(pick[k - 24])
+        if v not in vids:
+            vids.append(v)
+        kp_src.append(24 + vids.index(v))
+    if len(vids) > MAX_VERTS:
+        raise ValueError('pack_fit_model: at most %d distinct mesh vertices (got %d)' % (MAX_VERTS, len(vids)))
+    n = len(vids)
+    D = np.zeros((n, 3, KP), np.float32)
+    Wd = np.zeros((n, 24), np.float32)
+    pdv = pd.reshape(207, nv_mesh, 3)
+    for i, v in enumerate(vids):
+        D[i, :, 0] = vt[v]
+        D[i, :, 1:11] = sd[v]
+        D[i, :, 11:218] = pdv[:, v, :].T
+        Wd[i] = W[v]
+    return {'j_template': jt, 'j_shapedirs': js, 'parents': parents, 'vert_dirs': D, 'vert_w': Wd, 'kp_src': np.asarray(kp_src, np.int32),
+            'vertex_ids': np.asarray(vids, np.int64), 'n_verts': n, 'n_kp': len(kp_src)}
+
+
+def fit_keypoints_raw(model_struct, opts, est, est0, targets, conf, exp_avg, exp_avg_sq, energy, grad, best_est, best_energy, kp2d):
+    """one straps_fit_keypoints call on contiguous fp32 GPU tensors (None -> NULL); est [B,157] is updated in place"""
+    hipabi.check(hipabi.lib().straps_fit_keypoints(C.byref(model_struct), C.byref(opts), hipabi.ptr(est), hipabi.ptr(est0), hipabi.ptr(targets), hipabi.ptr(conf),
+                                                   hipabi.ptr(exp_avg), hipabi.ptr(exp_avg_sq), hipabi.ptr(energy), hipabi.ptr(grad), hipabi.ptr(best_est),
+                                                   hipabi.ptr(best_energy), hipabi.ptr(kp2d), est.shape[0], hipabi.stream_ptr()), 'straps_fit_keypoints')
+
+
+class KeypointFitter:
+    """`KeypointFitter(smpl)(cam, pose6d, shape, joints2D)` -> dict of device tensors; see the module docstring for what is minimised and
+    include/straps_hip.h for the exact objective.  smpl: the SMPL module (its device holds the tables).  lr: a float or a (cam, pose,
+    shape) triple.  The defaults are untuned on real data (module docstring)."""
+
+    def __init__(self, smpl, keypoints=None, iters=100, lr=0.01, robust_sigma=0.0, lambda_pose=1e-3, lambda_shape=1e-3,
+                 img_wh=config.REGRESSOR_IMG_WH, betas=(0.9, 0.999), eps=1e-8):
+        packed = pack_fit_model(smpl, keypoints)
+        hipabi.require_gpu_tensor(smpl._k_j_template, 'SMPL model buffers (call .to(device))')
+        dev = smpl._k_j_template.device
+        self.device, self.n_kp, self.n_verts = dev, packed['n_kp'], packed['n_verts']
+        self.vertex_ids = packed['vertex_ids']
+        self._tables = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)).to(dev))
+                        for k, v in packed.items() if k in ('j_template', 'j_shapedirs', 'parents', 'vert_dirs', 'vert_w', 'kp_src')}
+        s = hipabi.FitModelStruct()
+        for k, t in self._tables.items():
+            setattr(s, k, t.data_ptr() if t.numel() else None)
+        s.n_verts, s.n_kp = self.n_verts, self.n_kp
+        self._struct = s
+        lrs = tuple(float(v) for v in lr) if isinstance(lr, (tuple, list)) else (float(lr),) * 3
+        if len(lrs) != 3:
+            raise ValueError('KeypointFitter: lr is a float or a (cam, pose, shape) triple')
+        self.iters, self.lr, self.robust_sigma = int(iters), lrs, float(robust_sigma)
+        self.lambda_pose, self.lambda_shape, self.img_wh = float(lambda_pose), float(lambda_shape), float(img_wh)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+
+    def opts(self, iters=None, step0=0):
+        return hipabi.FitOptsStruct(self.iters if iters is None else int(iters), int(step0), self.lr[0], self.lr[1], self.lr[2], self.betas[0], self.betas[1],
+                                    self.eps, self.robust_sigma, self.lambda_pose, self.lambda_shape, self.img_wh)
+
+    def _inputs(self, cam, pose6d, shape, joints2D, conf, prior):
+        for t, nm, w in ((cam, 'cam', 3), (pose6d, 'pose6d', 144), (shape, 'shape', 10)):
+            hipabi.require_gpu_tensor(t, nm, torch.float32)
+            if t.dim() != 2 or t.shape[1] != w or t.shape[0] != cam.shape[0]:
+                raise RuntimeError('KeypointFitter: %s must be [B,%d], got %s' % (nm, w, tuple(t.shape)))
+        B = cam.shape[0]
+        hipabi.require_gpu_tensor(joints2D, 'joints2D')
+        if joints2D.dim() != 3 or joints2D.shape[0] != B or joints2D.shape[1] != self.n_kp or joints2D.shape[2] not in (2, 3):
+            raise RuntimeError('KeypointFitter: joints2D must be [%d,%d,2] or [%d,%d,3], got %s' % (B, self.n_kp, B, self.n_kp, tuple(joints2D.shape)))
+        est = torch.cat([cam.detach(), pose6d.detach(), shape.detach()], dim=1)
+        j = joints2D.detach().float()
+        if conf is None and j.shape[2] == 3:
+            conf = j[:, :, 2]
+        targets = j[:, :, :2].contiguous()
+        if conf is not None:
+            hipabi.require_gpu_tensor(conf, 'conf')
+            if tuple(conf.shape) != (B, self.n_kp):
+                raise RuntimeError('KeypointFitter: conf must be [%d,%d], got %s' % (B, self.n_kp, tuple(conf.shape)))
+            conf = conf.detach().float().contiguous()
+        est0 = None
+        if prior is not None:
+            for p in (prior if isinstance(prior, (tuple, list)) else (prior,)):
+                hipabi.require_gpu_tensor(p, 'prior', torch.float32)
+            est0 = (torch.cat([p.detach() for p in prior], dim=1) if isinstance(prior, (tuple, list)) else prior.detach()).contiguous()
+            if tuple(est0.shape) != (B, NE):
+                raise RuntimeError('KeypointFitter: prior must be [B,157] or a (cam, pose6d, shape) triple, got %s' % (tuple(est0.shape),))
+        return est, est0, targets, conf
+
+    @hipabi.on_tensor_device
+    def evaluate(self, cam, pose6d, shape, joints2D, conf=None, prior=None):
+        """-> (energy [B], grad [B,157], kp2d [B,K,2] normalised): the objective, its gradient and the projection at the given parameters"""
+        est, est0, targets, conf = self._inputs(cam, pose6d, shape, joints2D, conf, prior)
+        B = est.shape[0]
+        energy = torch.empty(B, 1, device=est.device, dtype=torch.float32)
+        grad = torch.empty(B, NE, device=est.device, dtype=torch.float32)
+        kp2d = torch.empty(B, self.n_kp, 2, device=est.device, dtype=torch.float32)
+        fit_keypoints_raw(self._struct, self.opts(0), est, est0, targets, conf, None, None, energy, grad, None, None, kp2d)
+        return energy[:, 0], grad, kp2d
+
+    @hipabi.on_tensor_device
+    def __call__(self, cam, pose6d, shape, joints2D, conf=None, prior=None, state=None, trace=False):
+        """cam [B,3], pose6d [B,144], shape [B,10], joints2D [B,K,2] or [B,K,3] in pixels of an img_wh square (a third column is the
+        confidence when `conf` is None), conf [B,K] or None, prior: the centre of the pose / shape priors ([B,157] or a triple; None = the
+        start), state: the 'state' of an earlier call (the Adam moments and step count go on from there).
+        -> {'cam_wp' [B,3], 'pose' [B,144], 'shape' [B,10], 'pose_rotmats' [B,24,3,3], 'energy0' [B], 'energy' [B] (at the returned
+        parameters), 'best': {'cam_wp', 'pose', 'shape', 'energy'} (the iterate of the smallest energy), 'joints2D' [B,K,2] (the fitted
+        projection, pixels), 'state', 'trace' [B,iters+1] if asked}.  The inputs are not modified.  Never synchronises; after one warm-up
+        call at the same shapes it can be captured in torch.cuda.graph."""
+        est, est0, targets, conf = self._inputs(cam, pose6d, shape, joints2D, conf, prior)
+        B, dev = est.shape[0], est.device
+        if state is None:
+            m, v, step0 = torch.zeros(B, NE, device=dev), torch.zeros(B, NE, device=dev), 0
+        else:
+            for k in ('exp_avg', 'exp_avg_sq'):
+                hipabi.require_gpu_tensor(state[k], "state['%s']" % k, torch.float32)
+                if tuple(state[k].shape) != (B, NE):
+                    raise RuntimeError("KeypointFitter: state['%s'] must be [%d,157], got %s" % (k, B, tuple(state[k].shape)))
+            # (contiguous copies: the call updates them in place, the caller's state stays as it was)
+            m, v = (state[k].detach().clone(memory_format=torch.contiguous_format) for k in ('exp_avg', 'exp_avg_sq'))
+            step0 = int(state['step'])
+        energy = torch.empty(B, self.iters + 1, device=dev, dtype=torch.float32)
+        best = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        best_e = torch.empty(B, device=dev, dtype=torch.float32)
+        kp2d = torch.empty(B, self.n_kp, 2, device=dev, dtype=torch.float32)
+        fit_keypoints_raw(self._struct, self.opts(step0=step0), est, est0, targets, conf, m, v, energy, None, best, best_e, kp2d)
+        pose = est[:, 3:147]
+        out = {'cam_wp': est[:, :3], 'pose': pose, 'shape': est[:, 147:], 'pose_rotmats': rot6d_to_rotmat(pose).view(B, 24, 3, 3),
+               'energy0': energy[:, 0], 'energy': energy[:, self.iters],
+               'best': {'cam_wp': best[:, :3], 'pose': best[:, 3:147], 'shape': best[:, 147:], 'energy': best_e},
+               'joints2D': cam_utils.undo_keypoint_normalisation(kp2d, self.img_wh),
+               'state': {'exp_avg': m, 'exp_avg_sq': v, 'step': step0 + self.iters}}
+        if trace:
+            out['trace'] = energy
+        return out

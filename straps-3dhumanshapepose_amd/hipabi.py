@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
-           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip']
+           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -142,6 +142,19 @@ def gemm_multi(descs):
 class RegressorDesc(C.Structure):
     """mirror of straps_regressor_desc_t"""
     _fields_ = [('layers', C.c_int32), ('in_channels', C.c_int32), ('ief_iters', C.c_int32), ('precision', C.c_int32)]
+
+
+class FitModelStruct(C.Structure):
+    """mirror of straps_fit_model_t"""
+    _fields_ = [('j_template', C.c_void_p), ('j_shapedirs', C.c_void_p), ('parents', C.c_void_p), ('vert_dirs', C.c_void_p), ('vert_w', C.c_void_p),
+                ('kp_src', C.c_void_p), ('n_verts', C.c_int32), ('n_kp', C.c_int32)]
+
+
+class FitOptsStruct(C.Structure):
+    """mirror of straps_fit_opts_t"""
+    _fields_ = [('iters', C.c_int32), ('step0', C.c_int32), ('lr_cam', C.c_float), ('lr_pose', C.c_float), ('lr_shape', C.c_float), ('beta1', C.c_float),
+                ('beta2', C.c_float), ('eps', C.c_float), ('robust_sigma', C.c_float), ('lambda_pose', C.c_float), ('lambda_shape', C.c_float),
+                ('img_wh', C.c_float)]
 
 
 _P, _I, _L, _F, _Z, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_double
@@ -276,6 +289,8 @@ SIGNATURES = {
     'straps_silhouette_counts': (_I, [_P, _P, _P, _L, _L, _P]),
     'straps_wp_silhouette_workspace_bytes': (_Z, [_L, _I]),
     'straps_wp_silhouette': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    # test-time fitting to 2-D keypoints, all iterations in one launch (csrc/fit.hip; added without a version change)
+    'straps_fit_keypoints': (_I, [C.POINTER(FitModelStruct), C.POINTER(FitOptsStruct)] + [_P] * 11 + [_L, _P]),
     'straps_comm_unique_id': (_I, [_P]),
     'straps_comm_init_rank': (_I, [_P, _I, _I, C.POINTER(C.c_void_p)]),
     'straps_comm_destroy': (_I, [_P]),

@@ -109,11 +109,36 @@ class Predictor:
         with torch.no_grad():
             proxy, jc, boxes = create_proxy_representation_batch(silhouettes, joints2D, self.out_wh, self.bbox_scale_factor, self.std)
             cam, pose, shape, rot = self.infer(proxy, rotmats=True)
-            B = proxy.shape[0]
-            rot = rot.view(B, 24, 3, 3)
-            shape = shape.contiguous()
-            verts, joints = self.smpl.forward_arrays(shape, rot)
-            v2d = cam_utils.undo_keypoint_normalisation(cam_utils.orthographic_project_torch(verts, cam), vis_wh or self.out_wh)
-            reposed, _ = self.smpl.forward_arrays(shape, self._identity_rotmats(B, proxy.device), want_joints=False)
+            return self._tail(proxy, cam, pose, shape, rot, jc, boxes, vis_wh)
+
+    def _tail(self, proxy, cam, pose, shape, rot, jc, boxes, vis_wh):
+        """parameters -> the result dict (under no_grad): SMPL forward, projection to pixels, reposed vertices"""
+        B = proxy.shape[0]
+        rot = rot.view(B, 24, 3, 3)
+        shape = shape.contiguous()
+        verts, joints = self.smpl.forward_arrays(shape, rot)
+        v2d = cam_utils.undo_keypoint_normalisation(cam_utils.orthographic_project_torch(verts, cam), vis_wh or self.out_wh)
+        reposed, _ = self.smpl.forward_arrays(shape, self._identity_rotmats(B, proxy.device), want_joints=False)
         return {'proxy_rep': proxy, 'cam_wp': cam, 'pose': pose, 'pose_rotmats': rot, 'shape': shape, 'vertices': verts, 'joints': joints,
                 'vertices2D': v2d, 'reposed_vertices': reposed, 'joints2D_cropped': jc, 'boxes': boxes, 'valid': boxes[:, 4] != 0}
+
+    @hipabi.on_tensor_device
+    def refine(self, out, fitter, conf=None):
+        """test-time fitting after the regressor: the parameters of `out` (a result of __call__) are fitted to out['joints2D_cropped'] by
+        `fitter` (a fit.KeypointFitter on this SMPL module, with as many keypoints as joints2D had; its img_wh must be this predictor's
+        out_wh: ValueError otherwise), with the regressor's answer as the centre of the priors.  conf [B,J] or None (all ones).  An invalid sample keeps its
+        parameters bit for bit: its confidences are zeroed.
+        -> a dict with the keys of __call__, rebuilt from the fitted parameters by the same tail, plus the fitter's 'energy0' and 'energy'
+        [B].  Never synchronises; capturable after a warm-up call."""
+        with torch.no_grad():
+            jc, valid = out['joints2D_cropped'], out['valid']
+            B = jc.shape[0]
+            if float(fitter.img_wh) != float(self.out_wh) or fitter.n_kp != jc.shape[1]:
+                raise ValueError('Predictor.refine: the fitter normalises targets by img_wh = %g and has %d keypoints; this predictor crops to %d pixels '
+                                 'and has %d joints' % (fitter.img_wh, fitter.n_kp, self.out_wh, jc.shape[1]))
+            conf = torch.ones(B, jc.shape[1], device=jc.device, dtype=torch.float32) if conf is None else conf.float()
+            conf = conf * valid[:, None].to(conf.dtype)
+            fit = fitter(out['cam_wp'].contiguous(), out['pose'].contiguous(), out['shape'].contiguous(), jc, conf=conf)
+            res = self._tail(out['proxy_rep'], fit['cam_wp'], fit['pose'], fit['shape'], fit['pose_rotmats'], jc, out['boxes'], None)
+        res['energy0'], res['energy'] = fit['energy0'], fit['energy']
+        return res
