@@ -983,6 +983,60 @@ int straps_fit_keypoints(const straps_fit_model_t* model, const straps_fit_opts_
         float* kp2d /*[B][n_kp][2] normalised projection at the last evaluation, or NULL*/,
         long long batch, void* stream);
 
+/* ---- the silhouette term of test-time fitting (csrc/silfit.hip; added without a version change) -----------------------------------
+ * The two-sided point-to-silhouette distance of SMPLify-style fitters: the projected vertices are pulled inside the target mask
+ * through a distance field, and the mask's foreground pixels pull their nearest projected vertex towards them.  No rasteriser.
+ *
+ * Conventions.  Masks are [B][wh][wh] uint8, any non-zero byte is foreground.  The pixel grid is that of straps_wp_silhouette and
+ * undo_keypoint_normalisation: a projected point p = (s (x + tx), s (y + ty)) (fp32, unfused) has the grid coordinate
+ * g = (p + 1) * wh / 2 - 0.5, so that pixel (r, c) sits at g = (c, r).  Residuals are scaled by 2 / wh: the normalised units of the
+ * keypoint term of straps_fit_keypoints.
+ *
+ * straps_distance_field: d2 [B][wh][wh] int32, d2[b][r][c] = min over the foreground (r', c') of frame b of (r - r')^2 + (c - c')^2
+ *   (exact; 0 on the foreground); a frame without foreground gets 2 * wh * wh everywhere, more than any real value.  1 <= wh <= 1024.
+ *   No workspace: the column pass writes its result into d2, the row pass finishes it in place.
+ *
+ * straps_silhouette_energy, per body, fp32, with nl = ceil(wh / lattice):
+ *   inside term   q = clamp(g_v, 0, wh - 1) per axis; o = |g_v - q|; cell i = min(floor(q), wh - 2), f = q - i per axis;
+ *                 D = bilinear interpolation of sqrtf((float)d2) at the four corners of the cell; rho_v = (D + o) * 2 / wh;
+ *                 E_in = (1 / nverts) sum_v rho_v^2.  On a clamped axis the derivative of D is zero and that of o is (g - q) / o; on a free
+ *                 axis it is the bilinear derivative of D.
+ *   outside term  lattice points a = (lattice * j, lattice * i), i, j = 0 .. nl - 1, valid iff mask[lattice * i][lattice * j] != 0;
+ *                 r_a = min_v |g_v - a| over the unclamped g_v, on fp32 squared distances fmaf(dy, dy, dx * dx): the lowest vertex index
+ *                 wins among equal ones; h_a = max(0, r_a - tau) * 2 / wh; E_out = (1 / max(1, n_valid)) sum_a h_a^2, whose gradient goes
+ *                 to the nearest vertex alone.
+ *   empty target  a body with d2[b][0][0] == 2 * wh * wh gets both energies 0, all gradients 0 and nearest -1.
+ *   outputs (each may be NULL, at least one must be given): energy2 [B][2] = { E_in, E_out } unweighted; dverts [B][nverts][3] = gradient
+ *   of w_in E_in + w_out E_out (the z column is written as 0); dcam [B][3] the same energy's gradient w.r.t. (s, tx, ty); nearest
+ *   [B][nl][nl] int32 = the nearest vertex of every lattice point, -1 at invalid points.  cam rows have the stride ld_cam >= 3.
+ *   workspace (8-byte aligned): straps_silhouette_energy_workspace_bytes = batch * (16 * (nverts + nl * nl + ceil(nverts / 256)) + 128) bytes, 0
+ *   for an invalid request.  2 <= wh <= 1024, lattice >= 1 (above wh - 1: the single point (0, 0)), 1 <= nverts <= 2^20, tau >= 0.
+ *
+ * straps_fit_adam: the update step of a fit loop composed of entry points.  Per body
+ *   g = g_kp [157] + (dcam [3] | dx6 [144] | dbetas [10])   (each of the four may be NULL = zero; nothing is added for a NULL),
+ *   E = fmaf(w_out, E_out, fmaf(w_in, E_in, e_kp))          (e_kp [B] NULL = 0; energy2 [B][2] NULL: E = e_kp),
+ *   then Adam per element with the learning rate of the element's block and exactly the formula of straps_fit_keypoints (bias
+ *   corrections in double, b^t by squaring, t = step + 1); of opts only lr_*, beta1, beta2 and eps are read.  energy[b * ld_energy + col]
+ *   = E and grad [B][157] = g when given.  (best_est, best_energy), given together, hold the best iterate as straps_fit_keypoints keeps
+ *   it: with first != 0 they are set, otherwise replaced iff E < best_energy (the first minimum wins, a NaN never replaces what is held).
+ *   update == 0 only evaluates: est and the moments stay bit-identical (the final evaluation of a loop).
+ *
+ * All three check their arguments before any HIP call, launch on `stream`, allocate nothing, never synchronise, use no float atomics
+ * and are bit-reproducible; a body's result depends on nothing but that body's inputs.                                              */
+typedef struct {
+    int32_t wh, lattice;
+    float tau, w_in, w_out;     /* tau in pixels */
+} straps_silfit_opts_t;
+int straps_distance_field(const uint8_t* mask, int32_t* d2, long long batch, int wh, void* stream);
+size_t straps_silhouette_energy_workspace_bytes(long long batch, int nverts, int wh, int lattice);
+int straps_silhouette_energy(const float* verts, const float* cam, int ld_cam, const uint8_t* mask, const int32_t* d2,
+        const straps_silfit_opts_t* opts, float* energy2, float* dverts, float* dcam, int32_t* nearest,
+        void* workspace, long long batch, int nverts, void* stream);
+int straps_fit_adam(const straps_fit_opts_t* opts, float* est /*[B][157] in/out*/, const float* g_kp, const float* dcam,
+        const float* dx6, const float* dbetas, const float* e_kp, const float* energy2, float w_in, float w_out,
+        float* exp_avg, float* exp_avg_sq, float* energy, long long ld_energy, long long col, float* grad,
+        float* best_est, float* best_energy, int step, int first, int update, long long batch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

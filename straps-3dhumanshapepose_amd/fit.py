@@ -8,6 +8,12 @@ regressed joints (rows 45..89 of the 90-joint output) need the mesh and are refu
 
 The defaults (100 iterations, lr 0.01, lambda 1e-3) are the values of a float64 experiment on the synthetic model of this package: nobody
 has tuned them on real detections, and neither a real SMPL model nor detector output was available when they were chosen.
+
+`SilhouetteFitter` adds the silhouette the regressor was given to that objective (straps_distance_field, straps_silhouette_energy,
+straps_fit_adam: csrc/silfit.hip): the projected vertices are pulled inside the target mask through its distance field, the mask's
+foreground pixels pull their nearest projected vertex towards them.  That term needs the whole mesh, so its loop is a sequence of entry
+points per iteration (SMPL forward and backward included), not one launch.  Its default weights (100 on both silhouette terms, lattice 4,
+tau 1.5 px) are those of a float64 prototype on the synthetic model as well: untuned on real detections.
 """
 import ctypes as C
 
@@ -192,6 +198,151 @@ class KeypointFitter:
                'energy0': energy[:, 0], 'energy': energy[:, self.iters],
                'best': {'cam_wp': best[:, :3], 'pose': best[:, 3:147], 'shape': best[:, 147:], 'energy': best_e},
                'joints2D': cam_utils.undo_keypoint_normalisation(kp2d, self.img_wh),
+               'state': {'exp_avg': m, 'exp_avg_sq': v, 'step': step0 + self.iters}}
+        if trace:
+            out['trace'] = energy
+        return out
+
+
+def distance_field(masks):
+    """masks [B,wh,wh] (uint8, bool or float GPU tensor; compared with 0) -> int32 [B,wh,wh]: the exact squared Euclidean distance of every
+    pixel to the nearest foreground pixel of its frame, 2 * wh * wh in a frame without foreground (straps_distance_field)."""
+    hipabi.require_gpu_tensor(masks, 'masks')
+    if masks.dim() != 3 or masks.shape[1] != masks.shape[2] or masks.shape[0] < 1:
+        raise RuntimeError('distance_field: masks must be [B,wh,wh], got %s' % (tuple(masks.shape),))
+    m = masks.detach()
+    m = m.contiguous() if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)
+    d2 = torch.empty(m.shape, device=m.device, dtype=torch.int32)
+    hipabi.check(hipabi.lib().straps_distance_field(hipabi.ptr(m), hipabi.ptr(d2), m.shape[0], m.shape[1], hipabi.stream_ptr()), 'straps_distance_field')
+    return d2
+
+
+def silhouette_energy_raw(verts, cam, ld_cam, mask, d2, opts, energy2, dverts, dcam, nearest, workspace):
+    """one straps_silhouette_energy call on contiguous GPU tensors (None -> NULL); cam: a tensor or a raw device address"""
+    camp = C.c_void_p(cam) if isinstance(cam, int) else hipabi.ptr(cam)
+    hipabi.check(hipabi.lib().straps_silhouette_energy(hipabi.ptr(verts), camp, ld_cam, hipabi.ptr(mask), hipabi.ptr(d2), C.byref(opts), hipabi.ptr(energy2),
+                                                       hipabi.ptr(dverts), hipabi.ptr(dcam), hipabi.ptr(nearest), hipabi.ptr(workspace), verts.shape[0],
+                                                       verts.shape[1], hipabi.stream_ptr()), 'straps_silhouette_energy')
+
+
+def fit_adam_raw(opts, est, g_kp, dcam, dx6, dbetas, e_kp, energy2, w_in, w_out, exp_avg, exp_avg_sq, energy, col, grad, best_est, best_energy,
+                 step, first, update):
+    """one straps_fit_adam call on contiguous fp32 GPU tensors (None -> NULL); energy [B,ld] receives column `col`"""
+    hipabi.check(hipabi.lib().straps_fit_adam(C.byref(opts), hipabi.ptr(est), hipabi.ptr(g_kp), hipabi.ptr(dcam), hipabi.ptr(dx6), hipabi.ptr(dbetas), hipabi.ptr(e_kp),
+                                              hipabi.ptr(energy2), w_in, w_out, hipabi.ptr(exp_avg), hipabi.ptr(exp_avg_sq), hipabi.ptr(energy),
+                                              0 if energy is None else energy.shape[1], col, hipabi.ptr(grad), hipabi.ptr(best_est), hipabi.ptr(best_energy),
+                                              int(step), int(bool(first)), int(bool(update)), est.shape[0], hipabi.stream_ptr()), 'straps_fit_adam')
+
+
+class SilhouetteFitter(KeypointFitter):
+    """`SilhouetteFitter(smpl)(cam, pose6d, shape, silhouettes, joints2D)`: KeypointFitter's objective plus w_in E_in + w_out E_out of
+    straps_silhouette_energy (include/straps_hip.h) against the target masks, minimised by the same Adam.  lattice: spacing in pixels of the
+    target's foreground samples; tau: the distance in pixels below which a sample counts as covered.  joints2D=None fits the silhouette
+    and the priors alone.  The defaults are a float64 prototype's on the synthetic model, untuned on real detections (module docstring)."""
+
+    def __init__(self, smpl, keypoints=None, iters=100, lr=0.01, lattice=4, tau=1.5, w_in=100., w_out=100., robust_sigma=0.0, lambda_pose=1e-3,
+                 lambda_shape=1e-3, img_wh=config.REGRESSOR_IMG_WH, betas=(0.9, 0.999), eps=1e-8):
+        KeypointFitter.__init__(self, smpl, keypoints, iters, lr, robust_sigma, lambda_pose, lambda_shape, img_wh, betas, eps)
+        self.smpl = smpl
+        self.wh = int(img_wh)
+        if self.wh != img_wh or not 2 <= self.wh <= 1024:
+            raise ValueError('SilhouetteFitter: img_wh must be an integer in 2..1024 (got %r)' % (img_wh,))
+        if int(lattice) < 1 or not float(tau) >= 0:
+            raise ValueError('SilhouetteFitter: lattice must be at least 1 and tau must not be negative')
+        self.lattice, self.tau, self.w_in, self.w_out = int(lattice), float(tau), float(w_in), float(w_out)
+
+    def sil_opts(self):
+        return hipabi.SilFitOptsStruct(self.wh, self.lattice, self.tau, self.w_in, self.w_out)
+
+    def _sil_inputs(self, cam, pose6d, shape, silhouettes, joints2D, conf, prior):
+        hipabi.require_gpu_tensor(cam, 'cam', torch.float32)
+        B = cam.shape[0]
+        hipabi.require_gpu_tensor(silhouettes, 'silhouettes')
+        if tuple(silhouettes.shape) != (B, self.wh, self.wh):
+            raise RuntimeError('SilhouetteFitter: silhouettes must be [%d,%d,%d], got %s' % (B, self.wh, self.wh, tuple(silhouettes.shape)))
+        if joints2D is None:      # no keypoints: all confidences zero, the keypoint kernel supplies the priors alone
+            if conf is not None:
+                raise RuntimeError('SilhouetteFitter: conf without joints2D')
+            joints2D = torch.zeros(B, self.n_kp, 2, device=cam.device, dtype=torch.float32)
+            conf = torch.zeros(B, self.n_kp, device=cam.device, dtype=torch.float32)
+        est, est0, targets, conf = self._inputs(cam, pose6d, shape, joints2D, conf, prior)
+        if est0 is None:
+            est0 = est.clone()      # (the start: est itself moves)
+        s = silhouettes.detach()
+        mask = s.contiguous() if s.dtype == torch.uint8 else (s != 0).to(torch.uint8)
+        return est, est0, targets, conf, mask
+
+    def _buffers(self, B, dev, mask):
+        L = hipabi.lib()
+        f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
+        return {'d2': distance_field(mask), 'R': f(B, 24, 3, 3), 'betas': f(B, 10), 'verts': f(B, self.smpl.v_template.shape[0], 3),
+                'dverts': f(B, self.smpl.v_template.shape[0], 3), 'dcam': f(B, 3), 'energy2': f(B, 2), 'drot': f(B, 24, 3, 3), 'dbetas': f(B, 10),
+                'dx6': f(B, 144), 'e_kp': f(B, 1), 'g_kp': f(B, NE), 'est_kp': f(B, NE), 'kp2d': f(B, self.n_kp, 2),
+                'ws': torch.empty(L.straps_silhouette_energy_workspace_bytes(B, self.smpl.v_template.shape[0], self.wh, self.lattice) // 8, device=dev, dtype=torch.float64),
+                'ws_bwd': f(L.straps_smpl_bwd_workspace_bytes(B, 0) // 4)}
+
+    def _terms(self, est, est0, targets, conf, mask, buf):
+        """the six evaluating entry points of one iteration at `est` (steps 1 to 6 of the loop); the results are left in `buf`"""
+        L, st, B = hipabi.lib(), hipabi.stream_ptr(), est.shape[0]
+        x6 = C.c_void_p(est.data_ptr() + 12)
+        hipabi.check(L.straps_rot6d_fwd(x6, NE, 24, hipabi.ptr(buf['R']), B, st), 'straps_rot6d_fwd')
+        buf['betas'].copy_(est[:, 147:])
+        self.smpl.forward_arrays(buf['betas'], buf['R'], want_joints=False, out_verts=buf['verts'])
+        silhouette_energy_raw(buf['verts'], est, NE, mask, buf['d2'], self.sil_opts(), buf['energy2'], buf['dverts'], buf['dcam'], None, buf['ws'])
+        hipabi.check(L.straps_smpl_bwd(C.byref(self.smpl._model_struct()), hipabi.ptr(buf['betas']), hipabi.ptr(buf['R']), hipabi.ptr(buf['dverts']), None,
+                                       hipabi.ptr(buf['dbetas']), hipabi.ptr(buf['drot']), hipabi.ptr(buf['ws_bwd']), B, 0, st), 'straps_smpl_bwd')
+        hipabi.check(L.straps_rot6d_bwd(x6, NE, 24, hipabi.ptr(buf['drot']), hipabi.ptr(buf['dx6']), 144, B, st), 'straps_rot6d_bwd')
+        buf['est_kp'].copy_(est)      # (iters = 0 leaves it as it is; a copy keeps the loop's estimate out of the keypoint kernel's hands)
+        fit_keypoints_raw(self._struct, self.opts(0), buf['est_kp'], est0, targets, conf, None, None, buf['e_kp'], buf['g_kp'], None, None, buf['kp2d'])
+
+    @hipabi.on_tensor_device
+    def evaluate(self, cam, pose6d, shape, silhouettes, joints2D=None, conf=None, prior=None):
+        """-> (energy [B], grad [B,157], terms [B,3] = (E_kp including the priors, E_in, E_out; the silhouette terms unweighted)) at the given
+        parameters"""
+        est, est0, targets, conf, mask = self._sil_inputs(cam, pose6d, shape, silhouettes, joints2D, conf, prior)
+        B, dev = est.shape[0], est.device
+        buf = self._buffers(B, dev, mask)
+        self._terms(est, est0, targets, conf, mask, buf)
+        energy = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        grad = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        fit_adam_raw(self.opts(), est, buf['g_kp'], buf['dcam'], buf['dx6'], buf['dbetas'], buf['e_kp'], buf['energy2'], self.w_in, self.w_out, None, None,
+                     energy, 0, grad, None, None, 0, True, False)
+        return energy[:, 0], grad, torch.cat([buf['e_kp'], buf['energy2']], dim=1)
+
+    @hipabi.on_tensor_device
+    def __call__(self, cam, pose6d, shape, silhouettes, joints2D=None, conf=None, prior=None, state=None, trace=False):
+        """KeypointFitter.__call__ with the target masks `silhouettes` [B,img_wh,img_wh] (uint8, bool or float: compared with 0) as fourth
+        argument and joints2D optional.  -> the keys of KeypointFitter.__call__ plus 'energy_terms'
+        [B,3] = (E_kp including the priors, E_in, E_out) at the returned parameters.  iters + 1 evaluations, iters updates; every iteration
+        is rot6d forward, SMPL forward, straps_silhouette_energy, SMPL backward, rot6d backward, straps_fit_keypoints with iters = 0,
+        straps_fit_adam, on buffers allocated before the loop.  The inputs are not modified.  Never synchronises; after one warm-up call at
+        the same shapes it can be captured in torch.cuda.graph."""
+        est, est0, targets, conf, mask = self._sil_inputs(cam, pose6d, shape, silhouettes, joints2D, conf, prior)
+        B, dev = est.shape[0], est.device
+        if state is None:
+            m, v, step0 = torch.zeros(B, NE, device=dev), torch.zeros(B, NE, device=dev), 0
+        else:
+            for k in ('exp_avg', 'exp_avg_sq'):
+                hipabi.require_gpu_tensor(state[k], "state['%s']" % k, torch.float32)
+                if tuple(state[k].shape) != (B, NE):
+                    raise RuntimeError("SilhouetteFitter: state['%s'] must be [%d,157], got %s" % (k, B, tuple(state[k].shape)))
+            m, v = (state[k].detach().clone(memory_format=torch.contiguous_format) for k in ('exp_avg', 'exp_avg_sq'))
+            step0 = int(state['step'])
+        buf = self._buffers(B, dev, mask)
+        energy = torch.empty(B, self.iters + 1, device=dev, dtype=torch.float32)
+        best = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        best_e = torch.empty(B, device=dev, dtype=torch.float32)
+        opts = self.opts()
+        for i in range(self.iters + 1):
+            self._terms(est, est0, targets, conf, mask, buf)
+            fit_adam_raw(opts, est, buf['g_kp'], buf['dcam'], buf['dx6'], buf['dbetas'], buf['e_kp'], buf['energy2'], self.w_in, self.w_out, m, v,
+                         energy, i, None, best, best_e, step0 + i, i == 0, i < self.iters)
+        pose = est[:, 3:147]
+        out = {'cam_wp': est[:, :3], 'pose': pose, 'shape': est[:, 147:], 'pose_rotmats': buf['R'],
+               'energy0': energy[:, 0], 'energy': energy[:, self.iters],
+               'best': {'cam_wp': best[:, :3], 'pose': best[:, 3:147], 'shape': best[:, 147:], 'energy': best_e},
+               'energy_terms': torch.cat([buf['e_kp'], buf['energy2']], dim=1),
+               'joints2D': cam_utils.undo_keypoint_normalisation(buf['kp2d'], self.img_wh),
                'state': {'exp_avg': m, 'exp_avg_sq': v, 'step': step0 + self.iters}}
         if trace:
             out['trace'] = energy

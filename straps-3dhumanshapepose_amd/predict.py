@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import cam_utils, config, hipabi
+from .fit import SilhouetteFitter
 from .infer import InferenceRegressor
 
 _PATCHES = {}
@@ -125,7 +126,8 @@ class Predictor:
     @hipabi.on_tensor_device
     def refine(self, out, fitter, conf=None):
         """test-time fitting after the regressor: the parameters of `out` (a result of __call__) are fitted to out['joints2D_cropped'] by
-        `fitter` (a fit.KeypointFitter on this SMPL module, with as many keypoints as joints2D had; its img_wh must be this predictor's
+        `fitter` (a fit.KeypointFitter, or a fit.SilhouetteFitter -- then also to the silhouette the regressor was given, out['proxy_rep'][:, 0] != 0,
+        with 'energy_terms' [B,3] among the results -- on this SMPL module, with as many keypoints as joints2D had; its img_wh must be this predictor's
         out_wh: ValueError otherwise), with the regressor's answer as the centre of the priors.  conf [B,J] or None (all ones).  An invalid sample keeps its
         parameters bit for bit: its confidences are zeroed.
         -> a dict with the keys of __call__, rebuilt from the fitted parameters by the same tail, plus the fitter's 'energy0' and 'energy'
@@ -138,7 +140,14 @@ class Predictor:
                                  'and has %d joints' % (fitter.img_wh, fitter.n_kp, self.out_wh, jc.shape[1]))
             conf = torch.ones(B, jc.shape[1], device=jc.device, dtype=torch.float32) if conf is None else conf.float()
             conf = conf * valid[:, None].to(conf.dtype)
-            fit = fitter(out['cam_wp'].contiguous(), out['pose'].contiguous(), out['shape'].contiguous(), jc, conf=conf)
+            if isinstance(fitter, SilhouetteFitter):
+                # the silhouette the regressor was given is the target; an invalid sample's mask is emptied: with zero confidences every gradient is zero
+                target = (out['proxy_rep'][:, 0] != 0) & valid[:, None, None].to(torch.bool)
+                fit = fitter(out['cam_wp'].contiguous(), out['pose'].contiguous(), out['shape'].contiguous(), target, jc, conf=conf)
+            else:
+                fit = fitter(out['cam_wp'].contiguous(), out['pose'].contiguous(), out['shape'].contiguous(), jc, conf=conf)
             res = self._tail(out['proxy_rep'], fit['cam_wp'], fit['pose'], fit['shape'], fit['pose_rotmats'], jc, out['boxes'], None)
         res['energy0'], res['energy'] = fit['energy0'], fit['energy']
+        if 'energy_terms' in fit:
+            res['energy_terms'] = fit['energy_terms']
         return res

@@ -1,0 +1,58 @@
+"""GPU: straps_distance_field (csrc/silfit.hip) against the brute-force transform of tests/silfit_cases.py, exactly (torch.equal).
+
+Sizes 1, 2, 3, 16, 17, 64, 65, 256 (one lane per column in waves of 64, rows of 256 lanes per trip: both ragged and whole), batches of 1 and
+3, every mask case: empty, full, one pixel in each corner, random at density 0.4 (foreground bytes 2 and 255) and 0.01, and an empty frame
+between two non-empty ones.  The output sits behind redzone guards, the mask ends against a NaN margin."""
+import numpy as np
+import pytest
+import torch
+
+import silfit_cases as SC
+from redzone import Zone
+from smpl_cases import cpu_threads
+from straps_amd import fit, hipabi
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def dev():
+    assert torch.cuda.is_available(), 'GPU tests need a GPU'
+    hipabi.load()
+    torch.set_num_threads(cpu_threads())
+    return torch.device('cuda:0')
+
+
+def at_end_bytes(t, dev):
+    """a uint8 tensor whose last byte is followed by a margin of 0xFF bytes (foreground, were it read)"""
+    n = t.numel()
+    base = torch.full((256 + n + 65536,), 255, dtype=torch.uint8, device=dev)
+    out = base[256:256 + n].view(t.shape)
+    out.copy_(t)
+    return out
+
+
+@pytest.mark.parametrize('wh', [1, 2, 3, 16, 17, 64, 65, 256])
+def test_distance_field_is_exact(dev, wh):
+    for names, masks in SC.mask_batches(wh):
+        want = torch.from_numpy(np.stack([SC.reference_d2(wh, n) for n in names]))
+        z = Zone(dev)
+        d2 = z.guarded(masks.shape, dtype=torch.int32, fill=-7, name='d2')
+        m = at_end_bytes(torch.from_numpy(masks), dev)
+        hipabi.check(hipabi.lib().straps_distance_field(hipabi.ptr(m), hipabi.ptr(d2), masks.shape[0], wh, hipabi.stream_ptr()), 'straps_distance_field')
+        z.check()
+        assert torch.equal(d2.cpu(), want), (wh, names)
+        if 'empty' in names:
+            assert bool((d2[names.index('empty')] == 2 * wh * wh).all())
+
+
+def test_python_entry_takes_bool_and_float_masks_and_is_reproducible(dev):
+    wh = 17
+    m = torch.from_numpy(np.stack([SC.mask_cases(wh)[n] for n in ('rand04', 'empty', 'rand001')])).to(dev)
+    want = torch.from_numpy(np.stack([SC.reference_d2(wh, n) for n in ('rand04', 'empty', 'rand001')]))
+    a = fit.distance_field(m)
+    assert a.dtype == torch.int32 and torch.equal(a.cpu(), want)
+    assert torch.equal(fit.distance_field(m != 0), a) and torch.equal(fit.distance_field(m.float() * -0.5), a) and torch.equal(fit.distance_field(m), a)
+    assert torch.equal(fit.distance_field(m[2:3]), a[2:3])      # a frame alone equals the frame inside a batch
+    with pytest.raises(RuntimeError):
+        fit.distance_field(m[:, :5])
