@@ -2091,7 +2091,12 @@ extern "C" size_t straps_bn_bwd_workspace_bytes(long long rows, int c) {
 }
 
 extern "C" int straps_maxpool_fwd_idx(const float* x, float* y, uint8_t* idx, int batch, int h, int w, int c, void* stream) {
-    STRAPS_REQUIRE(x && y && idx && batch > 0 && (c & 3) == 0, "straps_maxpool_fwd_idx: bad arguments");
+    STRAPS_REQUIRE(x && y && idx, "straps_maxpool_fwd_idx: null pointer");
+    // (h = 0 would give Ho = (0 - 1) / 2 + 1 = 1 by C division: one row of -inf written into a zero-sized output)
+    STRAPS_REQUIRE(batch > 0, "straps_maxpool_fwd_idx: batch must be positive (batch=%d)", batch);
+    STRAPS_REQUIRE(h > 0, "straps_maxpool_fwd_idx: h must be positive (h=%d)", h);
+    STRAPS_REQUIRE(w > 0, "straps_maxpool_fwd_idx: w must be positive (w=%d)", w);
+    STRAPS_REQUIRE(c > 0 && (c & 3) == 0, "straps_maxpool_fwd_idx: c must be a positive multiple of 4 (c=%d)", c);
     const int Ho = (h - 1) / 2 + 1, Wo = (w - 1) / 2 + 1;
     const long long n = (long long)batch * Ho * Wo * (c >> 2);
     hipLaunchKernelGGL(maxpool_idx_kernel, dim3(capped_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, idx, batch, h, w, c, Ho, Wo);
@@ -2100,7 +2105,11 @@ extern "C" int straps_maxpool_fwd_idx(const float* x, float* y, uint8_t* idx, in
 }
 
 extern "C" int straps_maxpool_bwd(const float* dy, const uint8_t* idx, float* dx, int batch, int h, int w, int c, void* stream) {
-    STRAPS_REQUIRE(dy && idx && dx && batch > 0 && (c & 3) == 0, "straps_maxpool_bwd: bad arguments");
+    STRAPS_REQUIRE(dy && idx && dx, "straps_maxpool_bwd: null pointer");
+    STRAPS_REQUIRE(batch > 0, "straps_maxpool_bwd: batch must be positive (batch=%d)", batch);
+    STRAPS_REQUIRE(h > 0, "straps_maxpool_bwd: h must be positive (h=%d)", h);
+    STRAPS_REQUIRE(w > 0, "straps_maxpool_bwd: w must be positive (w=%d)", w);
+    STRAPS_REQUIRE(c > 0 && (c & 3) == 0, "straps_maxpool_bwd: c must be a positive multiple of 4 (c=%d)", c);
     const int Ho = (h - 1) / 2 + 1, Wo = (w - 1) / 2 + 1;
     const long long n = (long long)batch * h * w * (c >> 2);
     hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(capped_grid(n)), dim3(256), 0, (hipStream_t)stream, dy, idx, dx, batch, h, w, c, Ho, Wo);

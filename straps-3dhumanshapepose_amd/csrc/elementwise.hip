@@ -166,7 +166,7 @@ __global__ void bn_fold_kernel(const float* __restrict__ g, const float* __restr
     if (c >= C) return;
     const float sc = g[c] / sqrtf(var[c] + eps);
     scale[c] = sc;
-    shift[c] = b[c] - mean[c] * sc;
+    shift[c] = fmaf(-mean[c], sc, b[c]);      // (the contraction the compiler chose, spelled out: one rounding -- tests/test_gpu_norm_pool_edges.py restates it)
 }
 
 // MaxPool 3x3 / s2 / p1 over NHWC, one float4 of channels per thread
@@ -190,7 +190,10 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ 
                 const int wi = 2 * wo - 1 + s;
                 if ((unsigned)wi >= (unsigned)W) continue;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(x + (((long long)b * H + hi) * W + wi) * C + c4 * 4);
-                m[0] = fmaxf(m[0], v[0]); m[1] = fmaxf(m[1], v[1]); m[2] = fmaxf(m[2], v[2]); m[3] = fmaxf(m[3], v[3]);
+                // (not fmaxf, which drops a NaN: a NaN in the window is the window's maximum, as in maxpool_idx_kernel and in ATen)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (v[e] > m[e] || v[e] != v[e]) m[e] = v[e];
             }
         }
         *reinterpret_cast<f32x4*>(y + i * 4) = m;
@@ -224,13 +227,15 @@ __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const float* __r
         const float inv = (float)(1.0 / sqrt(var + (double)eps));
         const float sc = gamma[c] * inv;
         scale[c] = sc;
-        shift[c] = beta[c] - (float)mean * sc;
+        shift[c] = fmaf(-(float)mean, sc, beta[c]);      // (explicit: the contraction the compiler chose -- one rounding, restated by tests/test_gpu_norm_pool_edges.py)
         if (smean) smean[c] = (float)mean;
         if (sinv) sinv[c] = inv;
         if (rmean) {
             const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-            rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mean;
-            rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
+            // (explicit fmaf: left to the compiler, the running-mean line became two rounded products and an addition (v_pk_mul_f32, v_add_f32) beside a fused
+            //  running-variance line -- three roundings against two, which shows when the two terms cancel; tests/test_gpu_norm_pool_edges.py restates this form)
+            rmean[c] = fmaf(momentum, (float)mean, (1.f - momentum) * rmean[c]);
+            rvar[c] = fmaf(momentum, (float)unbiased, (1.f - momentum) * rvar[c]);
         }
     }
 }
@@ -300,7 +305,7 @@ __global__ void bn_fold_stats_kernel(const float* __restrict__ g, const float* _
     const float inv = 1.0f / sqrtf(var[c] + eps);
     const float sc = g[c] / sqrtf(var[c] + eps);          // (the same expression as bn_fold_kernel: identical scale / shift)
     scale[c] = sc;
-    shift[c] = b[c] - mean[c] * sc;
+    shift[c] = fmaf(-mean[c], sc, b[c]);
     smean[c] = mean[c];
     sinv[c] = inv;
 }

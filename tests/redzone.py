@@ -12,7 +12,7 @@ with NaN, so an element the kernel should have written and did not is a NaN in t
 
 `at_end_of_poison()` places an input so that its last byte is followed by a NaN margin (what test_dgrad_x3_with_fused_batchnorm_sums
 does by hand): a read past the operand's end becomes a NaN in the result.  2-byte element types (bf16 bit patterns as int16) get the bf16
-quiet-NaN pattern 0x7FC0 as margin.
+quiet-NaN pattern 0x7FC0 as margin; `at_end_of_poison_wide()` (what `Zone.at_end` calls) also takes 1- and 8-byte element types.
 
 `planes_with_gaps()` re-homes a [3][ps] int16 plane operand (straps_split3_bf16[_cm], the weight packs) as [3][ps'] with ps' > n: split3 always
 gives ps == n rounded up to 8, so a read past plane 0 lands in plane 1 -- finite, plausible data.  Here every plane is followed by a gap of
@@ -27,6 +27,7 @@ MARGIN = 64 << 10                 # bytes on either side (the widest row stride 
 ALIGN = 256                       # the body starts on a 256-byte boundary, as a tensor of the caching allocator would
 SENTINEL = 0x7FC0BEEF             # a quiet-NaN bit pattern with a payload, as int32: a stray READ of a margin is a NaN as well
 BF16_NAN = 0x7FC0                 # bf16 quiet NaN (as int16: 32704): the margin / gap word of 2-byte plane tensors
+BYTE_POISON = 4                   # margin byte of 1-byte operands (arg-max taps, tile maps): a VALID tap on purpose, see at_end_of_poison_wide
 PLANE_GAP = MARGIN // 2           # default gap behind a plane, in 2-byte elements (a 256-row tile of one 32-channel chunk is 8 192 elements)
 
 
@@ -76,7 +77,7 @@ class Zone:
     """the guards of one test: z.guarded(...) like the module function, z.check() checks them all."""
 
     def __init__(self, device):
-        self.device, self.guards = device, []
+        self.device, self.guards, self.operands = device, [], []
 
     def guarded(self, shape, dtype=torch.float32, fill=float('nan'), margin=MARGIN, name=''):
         g = Guard(shape, dtype, self.device, fill, margin, name or 'buffer %d' % len(self.guards))
@@ -84,7 +85,10 @@ class Zone:
         return g.view
 
     def at_end(self, t):
-        return at_end_of_poison(t, self.device)
+        # (the zone keeps the operand alive: a call that passes hipabi.ptr(z.at_end(t)) would otherwise hand over memory the allocator has taken back)
+        out = at_end_of_poison_wide(t, self.device)
+        self.operands.append(out)
+        return out
 
     def planes(self, planes, n, gap=PLANE_GAP):
         return planes_with_gaps(planes, n, self.device, gap)
@@ -163,6 +167,30 @@ def at_end_of_poison(t, device=None, margin=MARGIN):
     base = torch.full((front + n + margin // 4,), float('nan'), dtype=torch.float32, device=device)
     body = base[front:front + n]
     out = body.view(t.dtype).view(t.shape) if t.dtype != torch.float32 else body.view(t.shape)
+    out.copy_(t)
+    return out
+
+
+def at_end_of_poison_wide(t, device=None, margin=MARGIN):
+    """at_end_of_poison for the operands of the BatchNorm / pooling kernels as well: 1-byte element types (arg-max taps, tile maps) get a margin of
+    BYTE_POISON -- bytes have no NaN.  The trade-off: a byte outside 0..8 (0xEE, say) could never be a right tap and would be easier to attribute, but
+    bn_bwd_reduce_pooled_kernel gathers raw at the position its tap names -- tap 0xEE is 79 rows below the window, far outside the tensor, and a test
+    helper must not turn an over-read of one byte into a wild read.  The centre tap stays inside the window; it shows because the gradient operand read
+    at the same offset is NaN there, and as a tile-map byte it marks an inactive tile active, whose NaN prefill is then overwritten -- and 8-byte ones (double partial sums) a
+    margin of fp64 NaNs (two fp32 NaN words side by side are a FINITE double)"""
+    if t is None or t.element_size() in (2, 4):
+        return at_end_of_poison(t, device, margin)
+    device = t.device if device is None else device
+    t = t.contiguous()
+    assert t.element_size() in (1, 8), 'at_end_of_poison_wide: 1-, 2-, 4- and 8-byte element types only'
+    n = t.numel()
+    if t.element_size() == 8:
+        front = ALIGN // 8
+        base = torch.full((front + n + margin // 8,), float('nan'), dtype=torch.float64, device=device)
+        out = base[front:front + n].view(t.dtype).view(t.shape)
+    else:
+        base = torch.full((ALIGN + n + margin,), BYTE_POISON, dtype=torch.uint8, device=device)
+        out = base[ALIGN:ALIGN + n].view(t.dtype).view(t.shape)
     out.copy_(t)
     return out
 

@@ -106,3 +106,25 @@ def test_product_library_reads_no_measurement_switches(lib):
     for src in hipabi._existing_sources():
         txt = open(src).read()
         assert 'getenv' not in txt, '%s reads the environment' % os.path.basename(src)
+
+
+def test_pooling_entries_refuse_empty_shapes_before_any_launch(lib):
+    """straps_maxpool_fwd_idx / straps_maxpool_bwd refuse batch, h, w or c <= 0 with STRAPS_EINVAL and name the argument (h = 0 gave Ho = 1 by C division:
+    a row of -inf written into a zero-sized output); straps_bn_relu_maxpool_fwd_x3 and straps_maxpool_fwd already did.  The refusal comes before any HIP
+    call; the buffers would hold a 1 x 1 x 4-channel output all the same (tests/test_gpu_norm_pool_edges.py repeats this on device buffers)."""
+    buf = [(C.c_float * 16)() for _ in range(5)]
+    x, y, dx, sc, sh = (C.cast(b, C.c_void_p) for b in buf)
+    idx = C.cast((C.c_uint8 * 16)(), C.c_void_p)
+    for bad in ('batch', 'h', 'w', 'c'):
+        for value in (0, -1):
+            shape = dict(batch=1, h=1, w=1, c=4)
+            shape[bad] = value
+            a = (shape['batch'], shape['h'], shape['w'], shape['c'])
+            for name, call in (('straps_maxpool_fwd_idx', lambda: lib.straps_maxpool_fwd_idx(x, y, idx, *a, None)), ('straps_maxpool_bwd', lambda: lib.straps_maxpool_bwd(x, idx, dx, *a, None))):
+                rc = call()
+                msg = lib.straps_last_error().decode() if rc else ''
+                assert rc == 1 and name in msg and ('%s=%d' % (bad, value)) in msg, (name, rc, msg)
+            assert lib.straps_bn_relu_maxpool_fwd_x3(x, sc, sh, y, idx, None, 0, *a, None) == 1 and b'straps_bn_relu_maxpool_fwd' in lib.straps_last_error()
+            assert lib.straps_maxpool_fwd(x, y, *a, None) == 1
+    assert lib.straps_maxpool_fwd_idx(x, y, idx, 1, 1, 1, 6, None) == 1 and b'c=6' in lib.straps_last_error()
+    assert lib.straps_maxpool_fwd_idx(None, y, idx, 1, 1, 1, 4, None) == 1 and b'null pointer' in lib.straps_last_error()

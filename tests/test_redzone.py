@@ -132,3 +132,20 @@ def test_a_write_behind_the_last_plane_is_a_margin_hit():
     g.base[g.hi] = 1
     with pytest.raises(AssertionError, match='0 bytes past its end'):
         g.check()
+
+
+def test_at_end_of_poison_wide_takes_bytes_and_doubles():
+    t = torch.arange(11, dtype=torch.uint8).view(1, 11)
+    p = redzone.at_end_of_poison_wide(t)
+    assert torch.equal(p, t) and p.dtype == torch.uint8
+    whole, first = _whole(p, torch.uint8)
+    assert bool((whole[first + 11:] == redzone.BYTE_POISON).all()) and whole.numel() - first - 11 == redzone.MARGIN and bool((whole[:first] == redzone.BYTE_POISON).all())
+    d = redzone.at_end_of_poison_wide(torch.arange(5, dtype=torch.float64))
+    assert d.dtype == torch.float64 and d.tolist() == [0.0, 1.0, 2.0, 3.0, 4.0] and d.data_ptr() % 16 == 0
+    whole, first = _whole(d, torch.float64)
+    assert bool(torch.isnan(whole[first + 5:]).all()) and whole.numel() - first - 5 == redzone.MARGIN // 8 and bool(torch.isnan(whole[:first]).all())
+    f = redzone.at_end_of_poison_wide(torch.ones(3))
+    assert f.dtype == torch.float32 and f.tolist() == [1.0] * 3 and redzone.at_end_of_poison_wide(None) is None
+    z = redzone.Zone('cpu')
+    a = z.at_end(t)
+    assert z.operands[-1] is a                      # the zone keeps its operands alive
