@@ -1037,6 +1037,52 @@ int straps_fit_adam(const straps_fit_opts_t* opts, float* est /*[B][157] in/out*
         float* exp_avg, float* exp_avg_sq, float* energy, long long ld_energy, long long col, float* grad,
         float* best_est, float* best_energy, int step, int first, int update, long long batch, void* stream);
 
+/* ---- shaded picture of a mesh under the weak-perspective camera (csrc/render.hip; added without a version change) -----------------
+ * What predict/predict_3D.py:169-178 draws through renderers/weak_perspective_pyrender_renderer.py, for a batch, on the device.  The
+ * shading model is Lambert with an ambient term, NOT pyrender's metallic-roughness material: which face a pixel shows is defined
+ * exactly below, the colours are this model's, and parity with the reference's pixels is not claimed.
+ *
+ * Frame and pixel grid: those of straps_wp_silhouette.  Pixel (r, c) samples ((2c + 1 - wh) / wh, (2r + 1 - wh) / wh); rows run with
+ * +v, no flip.  The viewer looks along +z: NEARER means SMALLER z (the reference turns the mesh by 180 degrees about x and looks down
+ * -z, which is the same picture).  All arithmetic is fp32, unfused, in the order written here.
+ *   vertices     p' = R p, each row (R[3r] x + R[3r+1] y) + R[3r+2] z; rotation NULL: p' = p, no multiply; rotation_per_body == 0: one
+ *                row-major [3][3] matrix, otherwise [B][3][3].  u = s (x' + tx), v = s (y' + ty) with (s, tx, ty) = cam_wp[b * ld_cam ..].
+ *   normals      vertex normal = sum over the incident faces, in the order of the table, of cross(p1' - p0', p2' - p0') (not normalised).
+ *                The table is CSR: vf_offsets [nverts + 1] int32, non-decreasing from 0; vf_faces [vf_offsets[nverts]] int32 lists, per
+ *                vertex, the faces that hold it, ascending (a face that names a vertex twice is listed once); a face with an index
+ *                outside [0, nverts) is not listed.  Built once on the host from `faces`.  A gather: no atomics, bit-reproducible.
+ *   coverage     exactly straps_wp_silhouette's rule (two-sided, edges included, |e(v0,v1,v2)| <= 1e-12 or NaN and out-of-range faces
+ *                skipped).  Per covered sample w_k = e_k / e(v0,v1,v2), z = (w0 z0' + w1 z1') + w2 z2'; the sample goes to the face with
+ *                the smallest z, among equal z to the lowest face id (a 64-bit minimum over (order-preserving key of z, face id): no
+ *                dependence on any order).
+ *   shading      n = (w0 n0 + w1 n1) + w2 n2 per component with the winning face's weights, divided by sqrtf of its squared length
+ *                (nx nx + ny ny) + nz nz; a squared length below 1e-24 (or NaN) gives n = (0, 0, -1).  n is negated iff the z component
+ *                (x1' - x0') (y2' - y0') - (y1' - y0') (x2' - x0') of the winning face's own normal is positive -- one decision per
+ *                face, after the fallback.  lam = ambient, then lam = lam + intensity_l * max(0, (nx dx + ny dy) + nz dz) for l = 0 ..
+ *                n_lights - 1; c_k = colour[k] * min(lam, 1); byte = floor(255 * clamp(c_k, 0, 1) + 0.5).
+ *   outputs      rgb [B][wh][wh][3] uint8; mask [B][wh][wh] uint8 (1 covered, 0 not); depth [B][wh][wh] float (z of the winning face,
+ *                +inf where nothing covers); face_ids [B][wh][wh] int32 (-1 where nothing covers).  mask, depth and face_ids may be
+ *                NULL.  An uncovered pixel takes background[b][r][c][:] (uint8 [B][wh][wh][3]) or, when background is NULL, the
+ *                quantised opts->background.
+ * light_dir holds unit vectors from the surface towards the light, in this frame (not normalised here).  0 <= n_lights <= 4; ambient
+ * finite and >= 0.  workspace (8-byte aligned): straps_render_mesh_workspace_bytes = batch * (8 * wh * wh + 32 * nverts) bytes -- the
+ * z-buffer first, then p', (u, v) and the normals -- 0 for a non-positive argument or wh > 4096.  1 <= wh <= 4096, nfaces <= 715827882.
+ * Arguments are checked before any HIP call; five launches on `stream`, no allocation, no synchronisation, no floating-point atomics,
+ * nothing read that the call has not written: bit-reproducible.                                                                     */
+typedef struct {
+    float colour[3];
+    float ambient;
+    float background[3];
+    int32_t n_lights;
+    float light_dir[12];
+    float light_intensity[4];
+} straps_render_opts_t;
+size_t straps_render_mesh_workspace_bytes(long long batch, int nverts, int wh);
+int straps_render_mesh(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces,
+        const float* cam_wp, int ld_cam, const float* rotation, int rotation_per_body, const straps_render_opts_t* opts,
+        const uint8_t* background, uint8_t* rgb, uint8_t* mask, float* depth, int32_t* face_ids, void* workspace,
+        long long batch, int nverts, int nfaces, int wh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ from .train_abi import CompositeTrainer, flat_training_params, flat_bn_state  # 
 from .smpl import SMPL, ModelOutput, pack_smpl_model  # noqa: F401
 from .rigid_transform_utils import rot6d_to_rotmat, batch_rodrigues  # noqa: F401
 from .multi_task_loss import HomoscedasticUncertaintyWeightedMultiTaskLoss  # noqa: F401
-from .nmr_renderer import NMRRenderer, WeakPerspectiveSilhouetteRenderer  # noqa: F401
+from .nmr_renderer import NMRRenderer, WeakPerspectiveSilhouetteRenderer, WeakPerspectiveMeshRenderer, vertex_face_table  # noqa: F401
 from .metrics import EvalMetricsTracker  # noqa: F401
 from .predict import Predictor, create_proxy_representation_batch, heatmap_patch  # noqa: F401
 from .fit import KeypointFitter, SilhouetteFitter, distance_field, pack_fit_model  # noqa: F401

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
-           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip']
+           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'render.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -162,6 +162,12 @@ class SilFitOptsStruct(C.Structure):
     _fields_ = [('wh', C.c_int32), ('lattice', C.c_int32), ('tau', C.c_float), ('w_in', C.c_float), ('w_out', C.c_float)]
 
 
+class RenderOptsStruct(C.Structure):
+    """mirror of straps_render_opts_t"""
+    _fields_ = [('colour', C.c_float * 3), ('ambient', C.c_float), ('background', C.c_float * 3), ('n_lights', C.c_int32), ('light_dir', C.c_float * 12),
+                ('light_intensity', C.c_float * 4)]
+
+
 _P, _I, _L, _F, _Z, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes); must list every symbol of include/straps_hip.h (tests/test_abi.py checks)
@@ -301,6 +307,9 @@ SIGNATURES = {
     'straps_silhouette_energy_workspace_bytes': (_Z, [_L, _I, _I, _I]),
     'straps_silhouette_energy': (_I, [_P, _P, _I, _P, _P, C.POINTER(SilFitOptsStruct)] + [_P] * 5 + [_L, _I, _P]),
     'straps_fit_adam': (_I, [C.POINTER(FitOptsStruct)] + [_P] * 7 + [_F, _F] + [_P] * 3 + [_L, _L] + [_P] * 3 + [_I, _I, _I, _L, _P]),
+    # shaded weak-perspective mesh pictures (csrc/render.hip; added without a version change)
+    'straps_render_mesh_workspace_bytes': (_Z, [_L, _I, _I]),
+    'straps_render_mesh': (_I, [_P, _P, _P, _P, _P, _I, _P, _I, C.POINTER(RenderOptsStruct)] + [_P] * 6 + [_L, _I, _I, _I, _P]),
     'straps_comm_unique_id': (_I, [_P]),
     'straps_comm_init_rank': (_I, [_P, _I, _I, C.POINTER(C.c_void_p)]),
     'straps_comm_destroy': (_I, [_P]),

@@ -8,8 +8,8 @@ library call for the whole batch (straps_predict_proxy_input, csrc/predict.hip) 
 
 These are the PREDICT-side semantics, not the training-side ones of image_utils.batch_crop_and_resize / label_conversions: the window
 is not clamped to the frame (what sticks out reads as zero, and the joints are shifted by the unclamped corner), and the heat maps are
-the numpy ones (float64 joints truncated to int16, a float64 Gaussian).  The detectors, pad_to_square, the resize of the RGB image and
-all visualisation are not part of this package.
+the numpy ones (float64 joints truncated to int16, a float64 Gaussian).  The detectors, pad_to_square and the resize of the RGB image are
+not part of this package; of the visualisation, the two rendered pictures of predict_3D.py:169-178 are (`Predictor.render`).
 """
 import numpy as np
 import torch
@@ -88,6 +88,7 @@ class Predictor:
         self.smpl = smpl
         self.out_wh, self.bbox_scale_factor, self.std = int(out_wh), float(bbox_scale_factor), int(std)
         self._identity = None
+        self._render_consts = {}
 
     def refresh(self):
         self.infer.refresh()
@@ -151,3 +152,24 @@ class Predictor:
         if 'energy_terms' in fit:
             res['energy_terms'] = fit['energy_terms']
         return res
+
+    @hipabi.on_tensor_device
+    def render(self, out, renderer, images=None):
+        """predict_3D.py:170-174 for the batch: `out` a result of __call__ or refine, `renderer` a nmr_renderer.WeakPerspectiveMeshRenderer on the
+        same GPU, images None or uint8 [B,wh,wh,3] on the GPU (the pictures the predictions are drawn over; wh must be renderer.img_wh:
+        ValueError otherwise).
+        -> {'rend': out['vertices'] under out['cam_wp'] over `images` (over the renderer's background colour without them),
+            'reposed': out['reposed_vertices'] under the camera [0.8, 0, -0.2], turned by 180 degrees about x, over the background colour},
+        uint8 [B,wh,wh,3] each.  Never synchronises after the first call on a device (which uploads the two constants); capturable after it."""
+        verts = out['vertices']
+        B, wh = verts.shape[0], renderer.img_wh
+        if images is not None and (images.dim() != 4 or tuple(images.shape[1:3]) != (wh, wh)):
+            raise ValueError('Predictor.render: the renderer draws %d x %d pictures, `images` is %s' % (wh, wh, tuple(images.shape)))
+        key = str(verts.device)
+        if key not in self._render_consts:
+            self._render_consts[key] = (torch.tensor([0.8, 0.0, -0.2], device=verts.device, dtype=torch.float32),
+                                        torch.tensor([[1.0, 0.0, 0.0], [0.0, -1.0, 0.0], [0.0, 0.0, -1.0]], device=verts.device, dtype=torch.float32))
+        cam, rx180 = self._render_consts[key]
+        with torch.no_grad():
+            return {'rend': renderer(verts, out['cam_wp'], background=images),
+                    'reposed': renderer(out['reposed_vertices'], cam.expand(B, 3).contiguous(), rotation=rx180)}
