@@ -22,6 +22,21 @@ namespace {
 constexpr int KP = STRAPS_SMPL_KP, KG = KP / 8, NT = STRAPS_SMPL_TILES, NV = STRAPS_SMPL_V, NROUNDS = NT / 4;
 constexpr int BT = 32, AS = 292, SS = 193;        // SS: stage row = 32 vertices x (g[3], v_posed[3]) + 1
 constexpr int NJS = STRAPS_SMPL_NPICK + STRAPS_SMPL_NEXTRA;   // 66 joint-gradient sources (joints 24..89)
+// look-ahead of smpl_verts_bwd_kernel: RD fragment groups (3 + 1 f32x4 per lane each) in phase 1, RT = 4 RD transposed fragments in phase 4;
+// SKP skinning entries per vertex row are fetched ahead of phase 3 (SMPL has 4 weights per vertex; a wider model's further entries are read in phase 3);
+// phase 3b reads its table entries EB at a time
+constexpr int RD = 4, RT = 4 * RD, SKP = 4, EB = 8;
+// chunk partials per batch of smpl_pose_bwd_kernel
+constexpr int PU = 9;
+static_assert(RD >= 1 && RT <= 84, "the rings are filled before their loops");
+
+// workgroup barrier that orders the LDS traffic only.  __syncthreads() also waits for every global load of the wave (here: as a call, the kernel's
+// target attribute keeps it from being inlined), which would end the look-ahead of the round loop at each of its four barriers
+__device__ __forceinline__ STRAPS_NO_PACKED_FP32 void lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
 
 __global__ __launch_bounds__(256, 1) STRAPS_NO_PACKED_FP32 void smpl_verts_bwd_kernel(straps_smpl_model_t m, const float* __restrict__ F,
                                                                 const float* __restrict__ Amat, const float* __restrict__ dverts,
@@ -66,49 +81,92 @@ __global__ __launch_bounds__(256, 1) STRAPS_NO_PACKED_FP32 void smpl_verts_bwd_k
 
     for (int rd = round0; rd < round1; ++rd) {
         const int tile = rd * 4 + wave;
-        // ---- (1) recompute v_posed for this tile ----
+        // ---- loads of the round, issued ahead of their phases (a wave alone on its SIMD has nothing else to hide a round trip behind) ----
+        // phase 1's ring: the first RD fragment groups and F steps
+        const f32x4* px = blend + ((long long)(tile * 3 + 0) * KG) * 64 + lane;
+        const f32x4* py = px + KG * 64;
+        const f32x4* pz = py + KG * 64;
+        int fo = (vbody ? bl : 0) * KP + 4 * h;
+        asm volatile("" : "+v"(fo));         // (the F row is the same in every round: left alone, its 28 steps are hoisted out of the round loop and spilled)
+        const float* frow = F + b0 * KP + fo;
+        f32x4 rx[RD], ry[RD], rz[RD], rf[RD];
+#pragma unroll
+        for (int s = 0; s < RD; ++s) {
+            if (s < KG) {
+                rx[s] = px[s * 64]; ry[s] = py[s * 64]; rz[s] = pz[s * 64];
+                rf[s] = *reinterpret_cast<const f32x4*>(frow + 8 * s);
+            }
+        }
+        // phase 2's dL/dverts elements of this lane and the table ranges of phases 2 and 3b: none depends on phase 1, all land while its MFMAs run.
+        // Element i = lane + 64 t of the [32 bodies][96] tile, t = 3 q + u: body 2 q + bu, column i0 - 96 bu; the bodies of the batch are
+        // q < dvn[u] (0 without dverts or for a column past the last vertex).  Past them a lane reads its last element again, or F[0] if it has
+        // none, and stages a zero: no branch around a load
+        const int ncol = min(96, (NV - tile * 32) * 3);
+        const float* dvp[3];
+        int dvn[3], dvq[3], dvs[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int i0 = lane + 64 * u, bu = i0 >= 96, c = i0 - 96 * bu;
+            dvn[u] = (dverts && c < ncol) ? (nb - bu + 1) / 2 : 0;
+            dvp[u] = dvn[u] > 0 ? dverts + (b0 + bu) * (long long)(NV * 3) + tile * 96 + c : F;
+            dvq[u] = dvn[u] > 0 ? 2 * NV * 3 : 0;
+            dvs[u] = bu * SS + (c / 3) * 6 + (c % 3);
+        }
+        float dvr[48];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+#pragma unroll
+            for (int u = 0; u < 3; ++u) dvr[3 * q + u] = dvp[u][min(q, max(dvn[u] - 1, 0)) * dvq[u]];
+        }
+        const int jr0 = m.jrt_ptr[tile], jr1 = m.jrt_ptr[tile + 1];
+        int de0[3], de1[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int j = wave + 4 * (2 * i + h);
+            de0[i] = m.dj_ptr[rd * 24 + j]; de1[i] = m.dj_ptr[rd * 24 + j + 1];
+        }
+        // ---- (1) recompute v_posed for this tile: group g's fragments were loaded RD groups ahead ----
         f32x16 ax, ay, az;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { ax[r] = 0.f; ay[r] = 0.f; az[r] = 0.f; }
-        {
-            const f32x4* px = blend + ((long long)(tile * 3 + 0) * KG) * 64 + lane;
-            const f32x4* py = px + KG * 64;
-            const f32x4* pz = py + KG * 64;
-            const float* frow = F + (b0 + (vbody ? bl : 0)) * KP + 4 * h;
-            f32x4 cx0 = px[0], cy0 = py[0], cz0 = pz[0];
-            f32x4 fn = *reinterpret_cast<const f32x4*>(frow);
-#pragma unroll 2
-            for (int g = 0; g < KG; ++g) {
-                f32x4 nx0 = cx0, ny0 = cy0, nz0 = cz0;
-                const f32x4 f0 = vbody ? fn : f32x4{0.f, 0.f, 0.f, 0.f};
-                if (g + 1 < KG) {
-                    nx0 = px[(g + 1) * 64]; ny0 = py[(g + 1) * 64]; nz0 = pz[(g + 1) * 64];
-                    fn = *reinterpret_cast<const f32x4*>(frow + 8 * (g + 1));
-                }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    ax = mfma32(cx0[e], f0[e], ax);
-                    ay = mfma32(cy0[e], f0[e], ay);
-                    az = mfma32(cz0[e], f0[e], az);
-                }
-                cx0 = nx0; cy0 = ny0; cz0 = nz0;
+        for (int g = 0; g < KG; ++g) {
+            const int s = g % RD;
+            const f32x4 f0 = vbody ? rf[s] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                ax = mfma32(rx[s][e], f0[e], ax);
+                ay = mfma32(ry[s][e], f0[e], ay);
+                az = mfma32(rz[s][e], f0[e], az);
+            }
+            if (g + RD < KG) {                     // refill the slot (the last RD groups load nothing: no read past the tile's fragments or the F row)
+                rx[s] = px[(g + RD) * 64]; ry[s] = py[(g + RD) * 64]; rz[s] = pz[(g + RD) * 64];
+                rf[s] = *reinterpret_cast<const f32x4*>(frow + 8 * (g + RD));
+            }
+            if (g == (RD < KG ? RD : KG) - 1) {    // phase 2's staging: the elements were requested before the refills, so the next group's wait covers them
+#pragma unroll
+                for (int t = 0; t < 48; ++t)
+                    mystage[(t / 3) * 2 * SS + dvs[t % 3]] = t / 3 < dvn[t % 3] ? dvr[t] : 0.f;
+            }
+            __builtin_amdgcn_sched_barrier(0);     // (left alone, the scheduler sinks every refill to the MFMA that reads it: one round trip per group)
+        }
+        float skw[16][SKP];
+        int skj[16][SKP];
+#pragma unroll
+        for (int k = 0; k < SKP; ++k) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int v = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int at = k < KW ? v * KW + k : 0;           // (an entry the model does not have: element 0, not used below)
+                skw[r][k] = m.skin_w[at]; skj[r][k] = m.skin_j[at];
             }
         }
-        // ---- (2) stage dL/dverts of this tile (coalesced rows), then add the joint-gradient contributions ----
-        {
-            const int ncol = min(96, (NV - tile * 32) * 3);
-            for (int i = lane; i < BT * 96; i += 64) {
-                const int b = i / 96, c = i - b * 96;
-                float v = 0.f;
-                if (dverts && b < nb && c < ncol) v = dverts[(b0 + b) * (long long)(NV * 3) + tile * 96 + c];
-                mystage[b * SS + (c / 3) * 6 + (c % 3)] = v;
-            }
-        }
-        __syncthreads();
+        // ---- (2) dL/dverts of this tile is staged (inside the loop above); add the joint-gradient contributions ----
+        lds_barrier();
         if (djoints && h == 0 && vbody) {
             const float* dj = djoints + (b0 + bl) * (STRAPS_SMPL_NJOINTS_OUT * 3) + 72;   // joints 24..89
-            const int e0 = m.jrt_ptr[tile], e1 = m.jrt_ptr[tile + 1];
-            for (int e = e0; e < e1; ++e) {
+            for (int e = jr0; e < jr1; ++e) {
                 const int code = m.jrt_code[e];
                 const float w = m.jrt_w[e];
                 float* sv = mystage + bl * SS + (code >> 8) * 6;
@@ -116,7 +174,7 @@ __global__ __launch_bounds__(256, 1) STRAPS_NO_PACKED_FP32 void smpl_verts_bwd_k
                 sv[0] = fmaf(w, g[0], sv[0]); sv[1] = fmaf(w, g[1], sv[1]); sv[2] = fmaf(w, g[2], sv[2]);
             }
         }
-        __syncthreads();
+        lds_barrier();
         // ---- (3) skinning backward per (body, vertex) ----
         {
             const float* Ab = As_ + bl * AS;
@@ -128,7 +186,20 @@ __global__ __launch_bounds__(256, 1) STRAPS_NO_PACKED_FP32 void smpl_verts_bwd_k
                 const float gx = sv[0], gy = sv[1], gz = sv[2];
                 sv[3] = ax[r]; sv[4] = ay[r]; sv[5] = az[r];              // v_posed, for the joint owners below
                 float t00 = 0.f, t01 = 0.f, t02 = 0.f, t10 = 0.f, t11 = 0.f, t12 = 0.f, t20 = 0.f, t21 = 0.f, t22 = 0.f;
-                for (int k = 0; k < KW; ++k) {
+#pragma unroll
+                for (int k = 0; k < SKP; ++k) {
+                    if (k < KW) {
+                        const float w = skw[r][k];
+                        const int jo = skj[r][k] * 12;
+                        const f32x4 a0 = *reinterpret_cast<const f32x4*>(Ab + jo);
+                        const f32x4 a1 = *reinterpret_cast<const f32x4*>(Ab + jo + 4);
+                        const f32x4 a2 = *reinterpret_cast<const f32x4*>(Ab + jo + 8);
+                        t00 += w * a0[0]; t01 += w * a0[1]; t02 += w * a0[2];
+                        t10 += w * a1[0]; t11 += w * a1[1]; t12 += w * a1[2];
+                        t20 += w * a2[0]; t21 += w * a2[1]; t22 += w * a2[2];
+                    }
+                }
+                for (int k = SKP; k < KW; ++k) {                          // (a model with more than SKP weights per vertex: the rest as they come)
                     const float w = m.skin_w[v * KW + k];
                     const int jo = m.skin_j[v * KW + k] * 12;
                     const f32x4 a0 = *reinterpret_cast<const f32x4*>(Ab + jo);
@@ -138,49 +209,59 @@ __global__ __launch_bounds__(256, 1) STRAPS_NO_PACKED_FP32 void smpl_verts_bwd_k
                     t10 += w * a1[0]; t11 += w * a1[1]; t12 += w * a1[2];
                     t20 += w * a2[0]; t21 += w * a2[1]; t22 += w * a2[2];
                 }
-                // g_vposed = T_R^T g
-                ax[r] = t00 * gx + t10 * gy + t20 * gz;
-                ay[r] = t01 * gx + t11 * gy + t21 * gz;
-                az[r] = t02 * gx + t12 * gy + t22 * gz;
+                // g_vposed = T_R^T g.  The fusion is written out: left as t00 * gx + t10 * gy + t20 * gz, WHICH product the compiler rounds on its own
+                // changes with the code around the expression, and with it the last bits of dF.  This is the form of the kernel before the look-ahead
+                // (its disassembly rounds t1c * gy alone in all 48 expressions); tools/smpl_bwd_latency_ab.py compares the bits with that library
+                ax[r] = fmaf(t20, gz, fmaf(t00, gx, t10 * gy));
+                ay[r] = fmaf(t21, gz, fmaf(t01, gx, t11 * gy));
+                az[r] = fmaf(t22, gz, fmaf(t02, gx, t12 * gy));
             }
         }
-        __syncthreads();   // all four tiles of the round are staged (g and v_posed)
+        // phase 4's ring: its first RT transposed fragments are on their way while phase 3b walks the joint tables
+        const f32x4* pt = blend_t + ((long long)tile * 3 * 7 * 4) * 64 + lane;
+        f32x4 rt[RT];
+#pragma unroll
+        for (int s = 0; s < RT; ++s) rt[s] = pt[s * 64];
+        __builtin_amdgcn_sched_barrier(0);
+        lds_barrier();   // all four tiles of the round are staged (g and v_posed)
         // ---- (3b) dA_j += w * g (x) [v_posed; 1], by joint owner, entries in table order ----
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            const int j = wave + 4 * (2 * i + h);
-            const int e0 = m.dj_ptr[rd * 24 + j], e1 = m.dj_ptr[rd * 24 + j + 1];
-            for (int e = e0; e < e1; ++e) {
-                const int code = m.dj_code[e];                            // tile_in_round << 5 | vertex row
-                const float w = m.dj_w[e];
-                const float* sv = stage + ((code >> 5) * BT + bl) * SS + (code & 31) * 6;
-                const float wx = w * sv[0], wy = w * sv[1], wz = w * sv[2];
-                const float x = sv[3], y = sv[4], z = sv[5];
-                dacc[i][0] = fmaf(wx, x, dacc[i][0]); dacc[i][1] = fmaf(wx, y, dacc[i][1]); dacc[i][2] = fmaf(wx, z, dacc[i][2]); dacc[i][3] += wx;
-                dacc[i][4] = fmaf(wy, x, dacc[i][4]); dacc[i][5] = fmaf(wy, y, dacc[i][5]); dacc[i][6] = fmaf(wy, z, dacc[i][6]); dacc[i][7] += wy;
-                dacc[i][8] = fmaf(wz, x, dacc[i][8]); dacc[i][9] = fmaf(wz, y, dacc[i][9]); dacc[i][10] = fmaf(wz, z, dacc[i][10]); dacc[i][11] += wz;
-            }
-        }
-        // ---- (4) dF^T[k][b] += sum_v D[k][v][c] * g_vposed[v][b][c] ----
-        {
-            const f32x4* pt = blend_t + ((long long)tile * 3 * 7 * 4) * 64 + lane;
+            for (int e = de0[i]; e < de1[i]; e += EB) {
+                int code[EB];                                             // tile_in_round << 5 | vertex row
+                float w[EB];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
+                for (int u = 0; u < EB; ++u) {                            // (past the joint's last entry: that entry again, not used)
+                    const int at = min(e + u, de1[i] - 1);
+                    code[u] = m.dj_code[at]; w[u] = m.dj_w[at];
+                }
 #pragma unroll
-                for (int f = 0; f < 7; ++f) {
-#pragma unroll
-                    for (int rq = 0; rq < 4; ++rq) {
-                        const f32x4 a = pt[((c * 7 + f) * 4 + rq) * 64];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float g = c == 0 ? ax[rq * 4 + e] : (c == 1 ? ay[rq * 4 + e] : az[rq * 4 + e]);
-                            accF[f] = mfma32(a[e], g, accF[f]);
-                        }
+                for (int u = 0; u < EB; ++u) {
+                    if (e + u < de1[i]) {
+                        const float* sv = stage + ((code[u] >> 5) * BT + bl) * SS + (code[u] & 31) * 6;
+                        const float wx = w[u] * sv[0], wy = w[u] * sv[1], wz = w[u] * sv[2];
+                        const float x = sv[3], y = sv[4], z = sv[5];
+                        dacc[i][0] = fmaf(wx, x, dacc[i][0]); dacc[i][1] = fmaf(wx, y, dacc[i][1]); dacc[i][2] = fmaf(wx, z, dacc[i][2]); dacc[i][3] += wx;
+                        dacc[i][4] = fmaf(wy, x, dacc[i][4]); dacc[i][5] = fmaf(wy, y, dacc[i][5]); dacc[i][6] = fmaf(wy, z, dacc[i][6]); dacc[i][7] += wy;
+                        dacc[i][8] = fmaf(wz, x, dacc[i][8]); dacc[i][9] = fmaf(wz, y, dacc[i][9]); dacc[i][10] = fmaf(wz, z, dacc[i][10]); dacc[i][11] += wz;
                     }
                 }
             }
         }
-        __syncthreads();
+        // ---- (4) dF^T[k][b] += sum_v D[k][v][c] * g_vposed[v][b][c]: fragment n = (c * 7 + f) * 4 + rq was loaded RT fragments ahead ----
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int n = 0; n < 84; ++n) {
+            const int c = n / 28, f = (n / 4) % 7, rq = n % 4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float g = c == 0 ? ax[rq * 4 + e] : (c == 1 ? ay[rq * 4 + e] : az[rq * 4 + e]);
+                accF[f] = mfma32(rt[n % RT][e], g, accF[f]);
+            }
+            if (n + RT < 84) rt[n % RT] = pt[(n + RT) * 64];              // refill the slot (nothing past the tile's 84 fragments)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        lds_barrier();
     }
     // ---- per-chunk partials ----
     // each wave holds dF sums over ITS tiles: fixed-order tree reduction over the 4 waves through the (now free)
@@ -243,6 +324,39 @@ __global__ __launch_bounds__(256, 1) STRAPS_NO_PACKED_FP32 void smpl_verts_bwd_k
 // compared on the disassembly).
 // (a lane exchange of the kernel below: ds_bpermute_b32, several in flight, waits placed by the compiler)
 __device__ __forceinline__ float lane_get(float value, int src) { return __shfl(value, src, 64); }
+// The chunk partials are read PU chunks at a time: every load of a batch is issued before the first add, the next batch (two register sets, taking
+// turns) before the adds of this one; the adds stay one chunk after the other, as in a plain loop over the chunks.
+__device__ __forceinline__ STRAPS_NO_PACKED_FP32 void pose_load_dA(float (&t)[PU][12], const float* p, long long stride) {
+#pragma unroll
+    for (int u = 0; u < PU; ++u)
+#pragma unroll
+        for (int e = 0; e < 12; ++e) t[u][e] = p[u * stride + e];
+}
+__device__ __forceinline__ STRAPS_NO_PACKED_FP32 void pose_add_dA(float (&gA)[12], const float (&t)[PU][12]) {
+#pragma unroll
+    for (int u = 0; u < PU; ++u)
+#pragma unroll
+        for (int e = 0; e < 12; ++e) gA[e] += t[u][e];
+}
+// (dF: nine pose-feature columns from fR on, and the shape column fB)
+__device__ __forceinline__ STRAPS_NO_PACKED_FP32 void pose_load_dF(float (&t)[PU][10], const float* p, long long stride, int fR, int fB) {
+#pragma unroll
+    for (int u = 0; u < PU; ++u) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) t[u][e] = p[u * stride + fR + e];
+        t[u][9] = p[u * stride + fB];
+    }
+}
+__device__ __forceinline__ STRAPS_NO_PACKED_FP32 void pose_add_dF(float (&gR)[9], float& gbeta, const float (&t)[PU][10], bool rot, bool shape) {
+#pragma unroll
+    for (int u = 0; u < PU; ++u) {
+        if (rot) {
+#pragma unroll
+            for (int e = 0; e < 9; ++e) gR[e] += t[u][e];
+        }
+        if (shape) gbeta += t[u][9];
+    }
+}
 // (AA: compile-time flag of the fused axis-angle epilogue, no runtime branch added.  AA = false is straps_smpl_bwd's kernel: the same arithmetic, bit-identical
 //  results; as a template instantiation the compiler unrolls the dbeta shuffle loop, same speed -- DESIGN, "Axis-angle gradients")
 template <bool AA>
@@ -259,6 +373,7 @@ __global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void smpl_pose_bwd_kerne
     const bool vj = j < 24;
     const long long bb = vb ? body : 0;
     const int jj = vj ? j : 0;
+    const bool act = vb && vj;
 
     float beta[10];
 #pragma unroll
@@ -283,6 +398,13 @@ __global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void smpl_pose_bwd_kerne
         const float jp = lane_get(J[c], src);
         rel[c] = (jj > 0) ? J[c] - jp : J[c];
     }
+    // dA partials: the first batch is requested here, behind every load the forward chain needs -- the chain itself needs none of it and hides it.
+    // A lane without a (body, joint) sums the partials of (0, 0) in the batches; nothing of such a lane reaches an output.
+    const float* pA = dAp + (bb * 24 + jj) * 12;
+    const long long sA = B * 288;
+    const int nbat = chunks / PU;
+    float tA[PU][12], tB[PU][12];
+    if (nbat > 0) pose_load_dA(tA, pA, sA);
     // forward chain: G (own global transform) and P (parent's rotation), recomputed
     float G[12], PR[9];
 #pragma unroll
@@ -311,9 +433,17 @@ __global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void smpl_pose_bwd_kerne
     float gA[12];
 #pragma unroll
     for (int e = 0; e < 12; ++e) gA[e] = 0.f;
-    if (vb && vj)
-        for (int c = 0; c < chunks; ++c) {
-            const float* p = dAp + (((long long)c * B + body) * 24 + j) * 12;
+#pragma unroll
+    for (int b = 0; b < NROUNDS / PU; ++b) {             // (no launch has more than NROUNDS chunks: resolve_rpc)
+        if (b < nbat) {
+            const int bn = b + 1 < nbat ? b + 1 : b;     // (behind the last batch: that batch again, not used -- a branch around the loads would
+            pose_load_dA(b & 1 ? tA : tB, pA + bn * PU * sA, sA);      //  make the compiler wait for them before the adds, at the join)
+            pose_add_dA(gA, b & 1 ? tB : tA);
+        }
+    }
+    if (act)
+        for (int c = nbat * PU; c < chunks; ++c) {
+            const float* p = pA + c * sA;
 #pragma unroll
             for (int e = 0; e < 12; ++e) gA[e] += p[e];
         }
@@ -332,6 +462,12 @@ __global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void smpl_pose_bwd_kerne
     int child[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) child[c] = m.children[jj * 3 + c];
+    // dF partials (this lane's nine pose-feature columns and its shape column): the first batch travels during the walk over the tree below
+    const float* pF = dFp + bb * KP;
+    const long long sF = B * KP;
+    const int fR = 11 + (j >= 1 && vj ? j - 1 : 0) * 9, fB = 1 + (j < 10 ? j : 0);
+    float tF[PU][10], tG[PU][10];
+    if (nbat > 0) pose_load_dF(tF, pF, sF, fR, fB);
     float gR[9];
 #pragma unroll
     for (int e = 0; e < 9; ++e) gR[e] = 0.f;
@@ -382,8 +518,16 @@ __global__ __launch_bounds__(256) STRAPS_NO_PACKED_FP32 void smpl_pose_bwd_kerne
     }
     // pose-feature and direct beta gradients from dF (sum of chunk partials)
     float gbeta_direct = 0.f;
+#pragma unroll
+    for (int b = 0; b < NROUNDS / PU; ++b) {
+        if (b < nbat) {
+            const int bn = b + 1 < nbat ? b + 1 : b;
+            pose_load_dF(b & 1 ? tF : tG, pF + bn * PU * sF, sF, fR, fB);
+            pose_add_dF(gR, gbeta_direct, b & 1 ? tG : tF, j >= 1, j < 10);
+        }
+    }
     if (vb && vj) {
-        for (int c = 0; c < chunks; ++c) {
+        for (int c = nbat * PU; c < chunks; ++c) {
             const float* p = dFp + ((long long)c * B + body) * KP;
             if (j >= 1) {
 #pragma unroll
