@@ -259,7 +259,7 @@ typedef struct {
      * skinning weight s = sum_v R[j,v] w[v,k] on bone k.  They ride through the same contraction
      * as extra tiles; joint j is the sum of virtual vertices [vj_ptr[j], vj_ptr[j+1]).           */
     const int32_t* vj_ptr;     /* [45 + 1] */
-    int32_t n_tiles;           /* 216 + virtual tiles, multiple of 8                            */
+    int32_t n_tiles;           /* 216 + virtual tiles, multiple of 8, at most 256 (straps_smpl_fwd refuses more) */
     int32_t reserved0;
     const int32_t* pick_ids;   /* [21] vertex ids appended as joints 24..44                    */
     /* ---- tables used only by straps_smpl_bwd (may be NULL for forward-only use) ---- */

@@ -1085,6 +1085,11 @@ void smpl_verts_w_kernel(straps_smpl_model_t m, const float* __restrict__ F, con
 // output scalar is then summed by one lane in ascending order -> deterministic, and bit-identical to the former one-thread-per-
 // scalar kernel, which re-read the row with 12-byte accesses (220 us at 65 536 bodies; now the 200 MB row read at HBM speed).
 constexpr int JW = 4;                      // bodies (waves) per workgroup of the joint kernel
+// its dynamic LDS, JW rows of (n_tiles - NT) * 96 floats, is launched as it is (never raised above the 64 KB every kernel may ask for):
+// 42 virtual tiles fit, 40 as a multiple of NW -> n_tiles <= 256.  45 non-negative regressor rows give at most 45 x 24 = 1080 virtual
+// vertices = 34 tiles (n_tiles 256 after the rounding); only rows with sign changes, each (joint, bone) pair split in two, pack to more.
+constexpr int NT_MAX = NT + (64 * 1024 / (JW * 96 * (int)sizeof(float))) / NW * NW;
+static_assert(NT_MAX == 256, "straps_hip.h and smpl.py (MAX_TILES) state this bound");
 __global__ __launch_bounds__(JW * 64) void smpl_joints_kernel(straps_smpl_model_t m, const float* __restrict__ verts,
                                                               const float* __restrict__ vout, float* __restrict__ joints,
                                                               long long B) {
@@ -1168,6 +1173,9 @@ extern "C" int straps_smpl_fwd(const straps_smpl_model_t* model, const float* be
     STRAPS_REQUIRE(model->skin_k >= 1 && model->skin_k <= 24, "straps_smpl_fwd: skin_k %d out of range", model->skin_k);
     STRAPS_REQUIRE(model->n_tiles >= NT && model->n_tiles % NW == 0 && model->vj_ptr,
                    "straps_smpl_fwd: n_tiles %d must be a multiple of %d >= %d with the virtual-vertex table set", model->n_tiles, NW, NT);
+    STRAPS_REQUIRE(model->n_tiles <= NT_MAX,
+                   "straps_smpl_fwd: n_tiles %d exceeds %d: the joint kernel keeps %d bodies' virtual-vertex rows of (n_tiles - %d) * 384 bytes in 64 KB of LDS",
+                   model->n_tiles, NT_MAX, JW, NT);
     hipStream_t st = (hipStream_t)stream;
     const int rounds = (joints ? model->n_tiles : NT) / NW;   // vertices only: the virtual (joint) tiles are skipped
     const int rpc = resolve_rpc(rounds, batch, chunks);

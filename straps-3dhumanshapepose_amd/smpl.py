@@ -20,6 +20,7 @@ ModelOutput = namedtuple('ModelOutput', ['vertices', 'joints', 'full_pose', 'bet
 ModelOutput.__new__.__defaults__ = (None,) * len(ModelOutput._fields)
 
 V, VPAD, TILES, KP = 6890, 6912, 216, 224
+MAX_TILES = 256     # csrc/smpl.hip NT_MAX: mesh + virtual-vertex tiles straps_smpl_fwd accepts
 # STRAPS_SMPL_EXACT_F32 / STRAPS_SMPL_SPLIT_F16 (blend contraction split) / STRAPS_SMPL_SPLIT_F16_LBS (blend + skinning split)
 PRECISIONS = {'fp32': 0, 'fp16x3': 1, 'fp16x3_lbs': 2, 'fp16x3_lbs_pd16': 3, 'fp16x3_lbs_p16': 4}
 KERNELS = {'auto': 0, 'wide': 0x100, 'narrow': 0x200, 'wide_builtin': 0x100 | 0x400}      # STRAPS_SMPL_KERNEL_WIDE / _NARROW, OR-ed into the mode argument
@@ -73,6 +74,10 @@ def pack_smpl_model(model):
     nvirt = len(vs_)
     vj_ptr = np.concatenate([[0], np.cumsum(vjn)]).astype(np.int32)
     n_tiles = ((TILES + (nvirt + 31) // 32 + 7) // 8) * 8
+    if n_tiles > MAX_TILES:
+        raise ValueError('pack_smpl_model: the 45 extra-joint regressor rows pack to %d virtual vertices = %d tiles; straps_smpl_fwd takes at most %d '
+                         '(its joint kernel keeps the virtual-vertex rows in 64 KB of LDS).  Rows without sign changes give at most 45 x 24 = 1080 '
+                         'virtual vertices (256 tiles); (joint, bone) pairs whose coefficients cancel are split in two' % (nvirt, n_tiles, MAX_TILES))
     Dall = np.zeros((KP, n_tiles * 32, 3), np.float32)
     Dall[:, :VPAD] = D
     if nvirt:
