@@ -546,6 +546,32 @@ size_t straps_conv_wgrad_workspace_bytes(int batch, int h, int w, int cin, int c
 int straps_conv_wgrad(const float* x_nhwc, const float* dy_nhwc, float* dw_oihw, void* workspace,
                       int batch, int h, int w, int cin, int cout, int kh, int kw, int stride,
                       int pad, int accumulate, void* stream);
+/* The plan of a weight-gradient call: which kernel the library launches for a geometry, with which grid and split-K extent (host
+ * arithmetic only, like straps_conv_x3_stat_blocks; added without a version change).  route: the operand form -- what
+ * straps_conv_wgrad, straps_conv_wgrad_x3 with planes, straps_conv_wgrad_x3f run.  Returns STRAPS_EINVAL for a geometry the route
+ * refuses.  The kernel's grid is tiles x splits; split k covers units [k * unit, min((k + 1) * unit, units)).                   */
+#define STRAPS_WG_ROUTE_F32 0     /* fp32 tensors */
+#define STRAPS_WG_ROUTE_PLANES 1  /* bf16 planes (falls back to the fp32 tensors where straps_conv_wgrad_x3_on_planes is 0) */
+#define STRAPS_WG_ROUTE_F32_1X1 2 /* fp32-operand 1x1 */
+#define STRAPS_WG_FAMILY_TAP_F32 0  /* conv_wgrad_kernel<bco, bci> */
+#define STRAPS_WG_FAMILY_HALO_F32 1 /* conv_wgrad3x3_kernel */
+#define STRAPS_WG_FAMILY_TAP_X3 2   /* conv_wgrad_x3_kernel<bco, bci> */
+#define STRAPS_WG_FAMILY_HALO_X3 3  /* conv_wgrad3x3_x3_kernel<chunk_px> */
+#define STRAPS_WG_FAMILY_TAP_X3F 4  /* conv_wgrad_x3f_kernel<bco, bci> */
+typedef struct straps_wgrad_plan_t {
+    int32_t family;
+    int32_t bco, bci;   /* channel block of a workgroup (halo families: 64 x 64, all nine taps) */
+    int32_t chunk_px;   /* halo families: pixels per chunk, 32 or 64; per-tap families: 0 */
+    int32_t tiles;      /* grid.x: taps x channel blocks (halo families: channel blocks) */
+    int32_t splits;     /* grid.y = split-K partials */
+    int32_t unit;       /* extent of a split: pixel rows (a multiple of 32), halo families: chunks */
+    int32_t units;      /* total extent: output pixels M, halo families: chunks */
+    int32_t taps;
+    int32_t lds_bytes;  /* dynamic LDS of the launch */
+    int64_t part_bytes; /* splits x cout x taps x cin floats of the workspace */
+} straps_wgrad_plan_t;
+int straps_conv_wgrad_plan(int route, int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad,
+                           straps_wgrad_plan_t* out);
 /* stem weight gradient straight from the NCHW input (its data gradient: straps_stem_dgrad below). */
 size_t straps_stem_wgrad_workspace_bytes(int batch, int cin, int h, int w);
 int straps_stem_wgrad(const float* x_nchw, const float* dy_nhwc, float* dw_oihw, void* workspace,

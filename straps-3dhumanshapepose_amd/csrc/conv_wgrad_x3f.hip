@@ -5,7 +5,7 @@
 //   the operand path -- x is then the RAW output of the previous convolution, and the normalised activation the forward pass never materialised
 //   (straps_conv_fwd_x3f with a_scale) is not materialised for the backward either.
 //
-//   The per-tap kernel on planes (backward.hip, conv_wgrad_x3_kernel) reads 6 B per operand element that the BatchNorm kernels had to write next to
+//   The per-tap kernel on planes (conv_wgrad_kernels.h, conv_wgrad_x3_kernel) reads 6 B per operand element that the BatchNorm kernels had to write next to
 //   or instead of the fp32 tensors, once per tile of the OTHER channel dimension.  Here a workgroup is persistent over a split of the pixels: 32
 //   pixels per step, both operand tiles fetched with 16-byte loads (a pixel's BC channels are BC * 4 contiguous bytes), split into their three bf16
 //   parts in registers (hardware conversion, as conv_x3f.hip) and written into the LDS image the transpose reads of the plane kernel expect ([32
@@ -13,9 +13,10 @@
 //   two register sets.  Channel blocks are chosen so that the SMALLER channel dimension is covered whole wherever it fits (64 <-> 256: every
 //   operand element is read exactly once).  Same six-product arithmetic, same split-K partial layout and fixed-order reduction as the plane kernel.
 #include "common.h"
+#include "conv_wgrad_plan.h"
 #include <utility>
 
-// fixed-order reduction of split-K partials [split][co][tap][ci] into OIHW (backward.hip)
+// fixed-order reduction of split-K partials [split][co][tap][ci] into OIHW (conv_wgrad.hip)
 int straps_internal_wgrad_reduce(const float* part, float* dw_oihw, int splits, int cout, int cin, int taps, int accumulate, hipStream_t st);
 
 namespace {
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(64 * WGO * WGI, 2) void conv_wgrad_x3f_kernel(Wgrad
         for (int c = 0; c < NI; ++c)
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[a][c][q] = 0.f;
-    // fragment addresses (backward.hip, conv_wgrad_x3_kernel): lane t = lane & 15 names row t >> 2 of a 4-pixel group and channel quad t & 3 of its 16-channel half
+    // fragment addresses (conv_wgrad_kernels.h, conv_wgrad_x3_kernel): lane t = lane & 15 names row t >> 2 of a 4-pixel group and channel quad t & 3 of its 16-channel half
     const int tt = lane & 15, ch16 = (lane >> 4) & 1, kh = lane >> 5;
     int fd[2][2][MI], fx[2][2][NI];                               // [k step][read][32-channel block]
 #pragma unroll
@@ -261,33 +262,15 @@ __global__ __launch_bounds__(64 * WGO * WGI, 2) void conv_wgrad_x3f_kernel(Wgrad
             }
 }
 
-// channel block of a layer: the smaller channel dimension whole where it fits beside 256 of the other (every element read once), else 256 x 128 /
-// 128 x 256 (the wide operand once, the narrow one twice), 64 x 64 for the 64 <-> 64 layer
-inline void wgrad_x3f_block(int cin, int cout, int* bco, int* bci) {
-    if (cout % 256 == 0 && cin == 64) { *bco = 256; *bci = 64; }
-    else if (cin % 256 == 0 && cout == 64) { *bco = 64; *bci = 256; }
-    else if (cout % 256 == 0 && cin % 128 == 0 && cout >= cin) { *bco = 256; *bci = 128; }
-    else if (cin % 256 == 0 && cout % 128 == 0) { *bco = 128; *bci = 256; }
-    else if (cout % 128 == 0 && cin % 128 == 0) { *bco = 128; *bci = 128; }
-    else { *bco = 64; *bci = 64; }
-}
-
-inline int wgrad_x3f_splits(long long M, int tiles, bool tiles_are_small = false) {
-    int s = ((tiles_are_small ? 512 : 256) + tiles - 1) / tiles;  // one eight-wave workgroup per CU (two four-wave ones)
-    const long long max_s = (M + 63) / 64;                        // at least two steps per split
-    if (s > max_s) s = (int)max_s;
-    return s < 1 ? 1 : s;
-}
-
 template <int BCO, int BCI, int WGO, int WGI>
-int launch_wgrad_x3f(const WgradFP& q, int tiles, int splits, hipStream_t st) {
-    const size_t lds = (size_t)2 * 3 * 32 * (BCO + BCI) * sizeof(u16);
+int launch_wgrad_x3f(const WgradFP& q, const straps_wgrad_plan_t& pl, hipStream_t st) {
+    const size_t lds = (size_t)pl.lds_bytes;      // two stages of [3 planes][32 pixels][BCO + BCI] bf16
     if (q.a_scale) {
         STRAPS_RAISE_LDS((conv_wgrad_x3f_kernel<BCO, BCI, WGO, WGI, true>), lds, "conv_wgrad_x3f_kernel");
-        hipLaunchKernelGGL((conv_wgrad_x3f_kernel<BCO, BCI, WGO, WGI, true>), dim3(tiles, splits), dim3(64 * WGO * WGI), lds, st, q);
+        hipLaunchKernelGGL((conv_wgrad_x3f_kernel<BCO, BCI, WGO, WGI, true>), dim3(pl.tiles, pl.splits), dim3(64 * WGO * WGI), lds, st, q);
     } else {
         STRAPS_RAISE_LDS((conv_wgrad_x3f_kernel<BCO, BCI, WGO, WGI, false>), lds, "conv_wgrad_x3f_kernel");
-        hipLaunchKernelGGL((conv_wgrad_x3f_kernel<BCO, BCI, WGO, WGI, false>), dim3(tiles, splits), dim3(64 * WGO * WGI), lds, st, q);
+        hipLaunchKernelGGL((conv_wgrad_x3f_kernel<BCO, BCI, WGO, WGI, false>), dim3(pl.tiles, pl.splits), dim3(64 * WGO * WGI), lds, st, q);
     }
     STRAPS_CHECK_LAUNCH("conv_wgrad_x3f_kernel");
     return STRAPS_OK;
@@ -296,11 +279,9 @@ int launch_wgrad_x3f(const WgradFP& q, int tiles, int splits, hipStream_t st) {
 }  // namespace
 
 extern "C" size_t straps_conv_wgrad_x3f_workspace_bytes(int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad) {
-    if (kh != 1 || kw != 1 || pad != 0 || stride < 1 || cin % 64 || cout % 64) return 0;
-    const long long M = (long long)batch * ((h - 1) / stride + 1) * ((w - 1) / stride + 1);
-    int bco, bci;
-    wgrad_x3f_block(cin, cout, &bco, &bci);
-    return (size_t)wgrad_x3f_splits(M, (cout / bco) * (cin / bci), bco == 64 && bci == 64) * cout * cin * sizeof(float);
+    WgradPlan pl;
+    const int rc = straps_internal_wgrad_plan("straps_conv_wgrad_x3f_workspace_bytes", STRAPS_WG_ROUTE_F32_1X1, batch, h, w, cin, cout, kh, kw, stride, pad, &pl);
+    return rc == STRAPS_OK ? (size_t)pl.q.part_bytes : 0;
 }
 
 // dW (OIHW [cout][cin][1][1]) of a 1x1 convolution from the fp32 tensors: x [batch][h][w][cin] (a_scale / a_shift / a_relu as in
@@ -309,31 +290,24 @@ extern "C" int straps_conv_wgrad_x3f(const float* x, const float* a_scale, const
                                      int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int accumulate, void* stream) {
     STRAPS_REQUIRE(x && dy && dw_oihw && workspace, "straps_conv_wgrad_x3f: null pointer");
     STRAPS_REQUIRE(kh == 1 && kw == 1 && pad == 0 && (stride == 1 || stride == 2), "straps_conv_wgrad_x3f: 1x1 filters without padding, stride 1 or 2 only");
-    STRAPS_REQUIRE(cin % 64 == 0 && cout % 64 == 0, "straps_conv_wgrad_x3f: need cin%%64==0 and cout%%64==0 (cin=%d cout=%d)", cin, cout);
     STRAPS_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "straps_conv_wgrad_x3f: a_scale and a_shift must be given together");
     STRAPS_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(a_scale) | reinterpret_cast<uintptr_t>(a_shift)) & 15) == 0,
                    "straps_conv_wgrad_x3f: x, dy, a_scale and a_shift must be 16-byte aligned");
-    WgradFP q;
-    q.x = x; q.dy = dy; q.a_scale = a_scale; q.a_shift = a_shift; q.a_relu = a_relu; q.part = (float*)workspace;
-    q.H = h; q.W = w; q.Cin = cin; q.Cout = cout; q.stride = stride;
-    q.Ho = (h - 1) / stride + 1; q.Wo = (w - 1) / stride + 1;
-    const long long M = (long long)batch * q.Ho * q.Wo;
-    STRAPS_REQUIRE(M < (1LL << 31) && M > 0, "straps_conv_wgrad_x3f: bad problem size");
-    q.M = (int)M;
-    int bco, bci;
-    wgrad_x3f_block(cin, cout, &bco, &bci);
-    q.ct = cout / bco; q.it = cin / bci;
-    const int tiles = q.ct * q.it;
-    const int splits = wgrad_x3f_splits(M, tiles, bco == 64 && bci == 64);
-    q.rows_per_split = (int)(((M + splits - 1) / splits + 31) / 32 * 32);
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (bco == 256 && bci == 64) rc = launch_wgrad_x3f<256, 64, 4, 2>(q, tiles, splits, st);
-    else if (bco == 64 && bci == 256) rc = launch_wgrad_x3f<64, 256, 2, 4>(q, tiles, splits, st);
-    else if (bco == 256 && bci == 128) rc = launch_wgrad_x3f<256, 128, 4, 2>(q, tiles, splits, st);
-    else if (bco == 128 && bci == 256) rc = launch_wgrad_x3f<128, 256, 2, 4>(q, tiles, splits, st);
-    else if (bco == 128 && bci == 128) rc = launch_wgrad_x3f<128, 128, 4, 2>(q, tiles, splits, st);
-    else rc = launch_wgrad_x3f<64, 64, 2, 2>(q, tiles, splits, st);
+    WgradPlan pl;
+    int rc = straps_internal_wgrad_plan("straps_conv_wgrad_x3f", STRAPS_WG_ROUTE_F32_1X1, batch, h, w, cin, cout, kh, kw, stride, pad, &pl);
     if (rc != STRAPS_OK) return rc;
-    return straps_internal_wgrad_reduce(q.part, dw_oihw, splits, cout, cin, 1, accumulate, st);
+    const WgradTapGeom& g = pl.tap;
+    const WgradFP q{x, dy, a_scale, a_shift, a_relu, (float*)workspace, g.H, g.W, g.Cin, g.Cout, g.stride, g.Ho, g.Wo, g.M, g.rows_per_split, g.ct, g.it};
+    hipStream_t st = (hipStream_t)stream;
+    switch (pl.q.bco * 1000 + pl.q.bci) {      // (the plan names no other block)
+    case 256064: rc = launch_wgrad_x3f<256, 64, 4, 2>(q, pl.q, st); break;
+    case 64256: rc = launch_wgrad_x3f<64, 256, 2, 4>(q, pl.q, st); break;
+    case 256128: rc = launch_wgrad_x3f<256, 128, 4, 2>(q, pl.q, st); break;
+    case 128256: rc = launch_wgrad_x3f<128, 256, 2, 4>(q, pl.q, st); break;
+    case 128128: rc = launch_wgrad_x3f<128, 128, 4, 2>(q, pl.q, st); break;
+    default: rc = launch_wgrad_x3f<64, 64, 2, 2>(q, pl.q, st); break;
+    }
+    if (rc != STRAPS_OK) return rc;
+    return straps_internal_wgrad_reduce(q.part, dw_oihw, pl.q.splits, cout, cin, 1, accumulate, st);
 }
+

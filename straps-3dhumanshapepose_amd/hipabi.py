@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
-           'smpl_bwd.hip', 'backward.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
+           'smpl_bwd.hip', 'backward.hip', 'conv_wgrad.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
            'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'render.hip']
 
 _lib = None
@@ -139,6 +139,15 @@ def gemm_multi(descs):
     check(lib().straps_gemm_multi(arr, len(descs), stream_ptr()), 'straps_gemm_multi')
 
 
+class WgradPlanStruct(C.Structure):
+    """mirror of straps_wgrad_plan_t"""
+    _fields_ = [(n, C.c_int32) for n in ('family', 'bco', 'bci', 'chunk_px', 'tiles', 'splits', 'unit', 'units', 'taps', 'lds_bytes')] + [('part_bytes', C.c_int64)]
+
+
+WG_ROUTE_F32, WG_ROUTE_PLANES, WG_ROUTE_F32_1X1 = 0, 1, 2      # STRAPS_WG_ROUTE_*
+WG_FAMILIES = ('wgrad_f32', 'wgrad3_f32', 'wgrad_x3', 'wgrad3_x3', 'wgrad_x3f')      # STRAPS_WG_FAMILY_* by value
+
+
 class RegressorDesc(C.Structure):
     """mirror of straps_regressor_desc_t"""
     _fields_ = [('layers', C.c_int32), ('in_channels', C.c_int32), ('ief_iters', C.c_int32), ('precision', C.c_int32)]
@@ -251,6 +260,8 @@ SIGNATURES = {
     'straps_conv_dgrad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'straps_conv_wgrad_workspace_bytes': (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
     'straps_conv_wgrad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # the plan of a weight-gradient call (host arithmetic only; added without a version change)
+    'straps_conv_wgrad_plan': (_I, [_I] * 10 + [C.POINTER(WgradPlanStruct)]),
     'straps_stem_wgrad_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     'straps_stem_wgrad': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'straps_stem_dgrad_weight_floats': (_Z, [_I]),

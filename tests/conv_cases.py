@@ -1,7 +1,7 @@
 """Test helper: the case tables of tests/test_gpu_conv_edges.py and a statement of WHICH KERNEL each case reaches.
 
-The convolution family (csrc/conv_x3.hip, conv_x3_lean.hip, conv_x3_kernels.h, conv_igemm.h, conv_x3f.hip, conv_wgrad_x3f.hip and the weight-gradient
-part of backward.hip) picks its kernel instantiation from the geometry by size rules.  This module restates those rules in Python -- limited to what
+The convolution family (csrc/conv_x3.hip, conv_x3_lean.hip, conv_x3_kernels.h, conv_igemm.h, conv_x3f.hip, conv_wgrad_x3f.hip and conv_wgrad.hip
+with its plan, conv_wgrad_plan.h) picks its kernel instantiation from the geometry by size rules.  This module restates those rules in Python -- limited to what
 the tables need -- so that every case can say which instantiation and which epilogue form the library runs for it:
 
     pick_tile_x3 / halo_patch_slots / halo_choice / lean_epilogue_choice / x3_route        the plane kernels (forward and data gradient)
@@ -261,7 +261,7 @@ def dgrad_x3f_bn_blocks(B, H, W, cin, cout, k, stride, pad, tile_cfg):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-# weight gradients (backward.hip, conv_wgrad_x3f.hip)
+# weight gradients (conv_wgrad.hip, conv_wgrad_x3f.hip)
 
 WPlan = namedtuple('WPlan', 'inst splits unit units tiles taps')      # unit: rows (pixels) or chunks per split; units: M or nchunks
 

@@ -2,6 +2,7 @@
 launch (block counts, workspace bytes, route queries; no compute calls -- there is no GPU here), the conditions the case tables of
 tests/test_gpu_conv_edges.py are named for, and the coverage statement: the tables together reach every instantiation the product library can
 dispatch to.  A later change of a size rule that moves a case off its kernel fails here instead of thinning the coverage quietly."""
+import ctypes as C
 import itertools
 
 import pytest
@@ -92,6 +93,68 @@ def test_weight_gradient_queries_agree_and_every_plan_stays_inside_the_advertise
             == pl.splits * co * ci * 4, (B, H, W, ci, co, s)
         assert pl.splits * pl.unit >= pl.units
     assert lib.straps_conv_wgrad_x3f_workspace_bytes(1, 8, 8, 64, 64, 3, 3, 1, 1) == K.wgrad_x3f_workspace_bytes(1, 8, 8, 64, 64, 3, 1, 1) == 0
+
+
+def _library_plan(lib, route, B, H, W, ci, co, k, s, pad):
+    """straps_conv_wgrad_plan -> (the plan in conv_cases.py's terms, the raw struct)"""
+    out = hipabi.WgradPlanStruct()
+    assert lib.straps_conv_wgrad_plan(route, B, H, W, ci, co, k, k, s, pad, C.byref(out)) == 0, lib.straps_last_error()
+    fam = hipabi.WG_FAMILIES[out.family]
+    inst = {'wgrad_f32': (fam, out.bco), 'wgrad3_f32': (fam,), 'wgrad3_x3': (fam, out.chunk_px)}.get(fam, (fam, out.bco, out.bci))
+    if fam in ('wgrad3_f32', 'wgrad3_x3'):
+        assert (out.bco, out.bci) == (64, 64) and out.chunk_px == (32 if fam == 'wgrad3_f32' else inst[1])
+    else:
+        assert out.chunk_px == 0 and (fam != 'wgrad_f32' or out.bco == out.bci)
+    return K.WPlan(inst, out.splits, out.unit, out.units, out.tiles, out.taps), out
+
+
+W3PX = 32 + 112          # csrc/conv_wgrad_plan.h
+
+
+def _lds_bytes(inst):
+    """dynamic LDS of an instantiation: the per-tap formula of conv_cases.wgrad_clamp (the fp32-operand kernel stages the same image); elsewhere the
+    constants of csrc/conv_wgrad.hip"""
+    if inst[0] == 'wgrad3_x3':
+        return {32: 2 * 3 * (32 + 128) * 64 * 2, 64: 2 * 3 * (64 + 136) * 64 * 2}[inst[1]]
+    if inst[0] == 'wgrad3_f32':
+        return 2 * 2 * W3PX * 64 * 4
+    if inst[0] == 'wgrad_f32':
+        return {64: 32 * 1024, 128: 64 * 1024}[inst[1]]
+    return 2 * 3 * 32 * (inst[1] + inst[2]) * 2
+
+
+def test_the_library_plan_is_the_restated_plan_field_by_field(lib):
+    """straps_conv_wgrad_plan shows the ONE plan that sizing, routing and launch read (csrc/conv_wgrad_plan.h): for every geometry and both operand
+    forms it equals conv_cases.wgrad_plan -- instantiation, splits, per-split extent, total extent, tiles, taps -- its partials are splits x Cout x
+    taps x Cin floats and fit the advertised workspace, its LDS is the instantiation's; the same for the fp32-operand 1x1 route."""
+    n = 0
+    for c in _wgrad_geometries():
+        B, H, W, ci, co, k, s = c
+        pad = K.pad_of(k)
+        adv = lib.straps_conv_wgrad_workspace_bytes(B, H, W, ci, co, k, k, s, pad)
+        for planes in (True, False):
+            want = K.wgrad_plan(B, H, W, ci, co, k, s, pad, planes)
+            got, raw = _library_plan(lib, hipabi.WG_ROUTE_PLANES if planes else hipabi.WG_ROUTE_F32, B, H, W, ci, co, k, s, pad)
+            assert got == want, (c, planes, got, want)
+            assert raw.part_bytes == want.splits * co * want.taps * ci * 4 <= adv, (c, planes, raw.part_bytes, adv)
+            assert raw.lds_bytes == _lds_bytes(want.inst), (c, planes, raw.lds_bytes)
+            if not planes:
+                assert raw.part_bytes == adv, c
+            n += 1
+        assert lib.straps_conv_wgrad_x3_on_planes(B, H, W, ci, co, k, k, s, pad) == int(K.wgrad_plan(B, H, W, ci, co, k, s, pad).inst[0] in ('wgrad_x3', 'wgrad3_x3')), c
+    assert n > 600
+    for (B, H, W, ci, co, s, bn) in K.WGRAD_X3F + [(b, h, w, ci, co, s, 0) for (b, h, w, ci, co, k, s) in _wgrad_geometries() if k == 1]:
+        want = K.wgrad_x3f_plan(B, H, W, ci, co, s, bn)
+        got, raw = _library_plan(lib, hipabi.WG_ROUTE_F32_1X1, B, H, W, ci, co, 1, s, 0)
+        assert got == want._replace(inst=want.inst[:3]), (B, H, W, ci, co, s, got, want)          # (the operand-path BatchNorm is the call's, not the plan's)
+        assert raw.part_bytes == want.splits * co * ci * 4 == lib.straps_conv_wgrad_x3f_workspace_bytes(B, H, W, ci, co, 1, 1, s, 0)
+        assert raw.lds_bytes == _lds_bytes(want.inst)
+    # geometries a route refuses: an error, no plan
+    out = hipabi.WgradPlanStruct()
+    assert lib.straps_conv_wgrad_plan(hipabi.WG_ROUTE_F32_1X1, 1, 8, 8, 64, 64, 3, 3, 1, 1, C.byref(out)) == 1 and b'1x1' in lib.straps_last_error()
+    assert lib.straps_conv_wgrad_plan(hipabi.WG_ROUTE_PLANES, 1, 8, 8, 32, 64, 3, 3, 1, 1, C.byref(out)) == 1 and b'cin%64' in lib.straps_last_error()
+    assert lib.straps_conv_wgrad_plan(7, 1, 8, 8, 64, 64, 3, 3, 1, 1, C.byref(out)) == 1
+    assert lib.straps_conv_wgrad_plan(hipabi.WG_ROUTE_F32, 1, 8, 8, 64, 64, 3, 3, 1, 1, None) == 1
 
 
 def test_the_tables_reach_every_instantiation_the_product_library_dispatches_to():
