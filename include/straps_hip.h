@@ -1109,6 +1109,51 @@ int straps_render_mesh(const float* verts, const int32_t* faces, const int32_t* 
         const uint8_t* background, uint8_t* rgb, uint8_t* mask, float* depth, int32_t* face_ids, void* workspace,
         long long batch, int nverts, int nfaces, int wh, void* stream);
 
+/* ---- body measurements of a batch of meshes (csrc/measure.hip; added without a version change) -------------------------------------
+ * Volume, surface area, extent along a direction, planar girths and lengths along anchor points, n_meas of them per body, in one call.
+ * Vertices and points are read as fp32; every product, sum, division and square root is done in double; each result is rounded to float
+ * once.  out [B][n_meas].  Not differentiable; girths are plane sections, not tape-measure (convex hull) girths; planes and directions
+ * are the same for every body of the batch (T-pose bodies: no per-body normals).
+ *   anchor       a names vertex a of the body when 0 <= a < nverts, points[b][a - nverts] when nverts <= a < nverts + n_points
+ *                (points [B][n_points][3], may be NULL when n_points == 0); -1 means "none".
+ *   selected     face f is selected iff its three indices lie in [0, nverts) and (part_mask == 0, or face_parts[f] < 32 and bit
+ *                face_parts[f] of part_mask is set).  A face with an index out of range is skipped, as straps_render_mesh skips it.
+ *                part_mask != 0 with face_parts == NULL is an argument error.  face_parts [nfaces] uint8.
+ *   VOLUME       (1/6) * sum over the selected faces of q0 . (q1 x q2), q_i = p_i - c, c = anchor[0] or the origin when it is -1.
+ *                Signed: negative for inward-facing winding.
+ *   AREA         (1/2) * sum over the selected faces of |(p1 - p0) x (p2 - p0)|.
+ *   EXTENT       max_v (dir . p_v) - min_v (dir . p_v) over all nverts vertices; anchors, points and part_mask are not read.  A NaN
+ *                among the products makes the result NaN (max and min propagate it).
+ *   GIRTH        the plane through o = anchor[0] (required) with normal dir (not normalised here).  d_i = dir . (p_i - o); vertex i is on
+ *                the positive side iff d_i >= 0 (a NaN is not).  A selected face contributes iff its three sides are not all equal; then
+ *                one vertex a stands alone on its side, and each of the two edges (a, b) from it gives x = p_a + t (p_b - p_a) with
+ *                t = d_a / (d_a - d_b); the face adds |x - x'|.  The result is the sum over the faces: 0 (not NaN) when the plane misses
+ *                every selected face.  The length per face is continuous in the vertex positions: a vertex at d near 0 is no tie case,
+ *                and the anchor vertex itself (d == 0 exactly) counts as positive.
+ *   PATH         sum_i |A_(i+1) - A_i| over anchor[0 .. k-1], the leading entries that are not -1, 2 <= k <= 4.
+ * Anchors a kind does not read are ignored (VOLUME, GIRTH: anchor[0]; PATH: the leading entries; AREA, EXTENT: none).
+ * Limits: 1 <= n_meas <= 32, 1 <= nverts <= 2^20, 0 <= n_points <= 64, 0 <= nfaces <= 715827882; nfaces == 0 (faces may then be NULL)
+ * only when no measurement is a VOLUME, AREA or GIRTH.  `meas` is a HOST array, copied by value into the launches.
+ * workspace (8-byte aligned): straps_measure_workspace_bytes
+ *     = batch * n_meas * 8 * (ceil(nfaces / 512) + 2 * ceil(nverts / 2048)) bytes
+ * -- per body one double per measurement and block of 512 faces, then (max, min) per measurement and block of 2048 vertices -- and 0 for
+ * an argument outside the limits above.  Two launches on `stream`: workgroups of 512 faces (the corners of a face are loaded once for all
+ * measurements) or 2048 vertices of ONE body write partial sums in double, then one thread per (body, measurement) adds them in index
+ * order.  Arguments are checked before any HIP call; no allocation, no synchronisation, no floating-point atomics, nothing read that the
+ * call has not written: bit-reproducible, and a body's row depends on that body's inputs alone (same bits alone or in a batch; a NaN in
+ * one body leaves the others untouched).                                                                                             */
+enum { STRAPS_MEASURE_VOLUME = 0, STRAPS_MEASURE_AREA = 1, STRAPS_MEASURE_EXTENT = 2, STRAPS_MEASURE_GIRTH = 3, STRAPS_MEASURE_PATH = 4 };
+typedef struct {
+    int32_t kind;
+    int32_t anchor[4];
+    float dir[3];
+    uint32_t part_mask;
+} straps_measure_t;
+size_t straps_measure_workspace_bytes(long long batch, int nverts, int nfaces, int n_meas);
+int straps_measure_mesh(const float* verts, const float* points, const int32_t* faces, const uint8_t* face_parts,
+        const straps_measure_t* meas, float* out, void* workspace, long long batch, int nverts, int n_points, int nfaces,
+        int n_meas, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

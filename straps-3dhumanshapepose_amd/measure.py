@@ -1,0 +1,227 @@
+"""Body measurements of a batch of meshes on the device: height, volume, surface area, girths and limb lengths (csrc/measure.hip,
+straps_measure_mesh; include/straps_hip.h states the definitions).
+
+    measurer = BodyMeasurer.from_smpl(smpl).to(device)            # the tables of the model, default_measurements()
+    m = measurer(vertices, joints)                                # {'values': [B,M] float32, 'height': [B], 'volume': [B], ...}
+    m = predictor.measure(out, measurer)                          # the predicted body in the T-pose
+
+A measurement is a spec made by one of the helpers below; `measurements` is a dict name -> spec (or a sequence of (name, spec)), at most 32.
+An anchor is an int (a vertex id) or ('joint', j): row j of the `joints` given to the call.  `parts` is an iterable of part labels (0..31)
+of the per-face table `face_parts` (this package's labels, synthetic_smpl.JOINT_TO_PART: 1 / 2 left / right arm, 3 head, 4 / 5 left / right leg,
+6 torso); None: every face.
+
+All arithmetic is double on fp32 vertices, rounded to float once; results are bit-reproducible and a body's row depends on that body alone.
+OUT OF SCOPE: gradients of measurements (the call is not differentiable); tape-measure girths (a girth here is the length of the plane
+section, which follows concavities; a tape spans them: convex hull of the section); measurements on posed meshes with per-body plane
+normals (planes and directions are shared by the batch, which suits bodies in one pose: the T-pose).
+"""
+import collections
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import config, hipabi
+
+Spec = collections.namedtuple('Spec', ('kind', 'anchors', 'direction', 'parts'))
+KIND_NAMES = ('volume', 'area', 'extent', 'girth', 'path')
+
+
+def _anchor(a, what):
+    if isinstance(a, (tuple, list)):
+        if len(a) != 2 or a[0] != 'joint' or int(a[1]) < 0:
+            raise ValueError("%s: an anchor is a vertex id or ('joint', j) (got %r)" % (what, a))
+        if int(a[1]) >= hipabi.MEASURE_MAX_POINTS:
+            raise ValueError('%s: joint anchors are limited to the first %d joints (got %r)' % (what, hipabi.MEASURE_MAX_POINTS, a))
+        return ('joint', int(a[1]))
+    if isinstance(a, (bool, float)) or int(a) != a or int(a) < 0:
+        raise ValueError("%s: an anchor is a vertex id or ('joint', j) (got %r)" % (what, a))
+    return int(a)
+
+
+def _direction(d, what):
+    d = tuple(float(x) for x in np.asarray(d, np.float64).reshape(-1))
+    if len(d) != 3 or not np.isfinite(d).all() or not any(d):
+        raise ValueError('%s: a direction is three finite numbers, not all zero (got %r)' % (what, d))
+    return d
+
+
+def _parts(parts, what):
+    if parts is None:
+        return None
+    parts = tuple(sorted(set(int(p) for p in parts)))
+    if not parts or parts[0] < 0 or parts[-1] > 31:
+        raise ValueError('%s: part labels are 0..31, at least one (got %r)' % (what, parts))
+    return parts
+
+
+def volume(parts=None, about=None):
+    """signed volume (1/6) sum q0 . (q1 x q2) of the selected faces, corners relative to the anchor `about` (None: the origin).  The choice of
+    `about` does not matter for a closed surface; for an open part it closes the part with a cone to that point."""
+    return Spec(hipabi.MEASURE_VOLUME, () if about is None else (_anchor(about, 'measure.volume'),), (0.0, 0.0, 0.0), _parts(parts, 'measure.volume'))
+
+
+def area(parts=None):
+    """surface area of the selected faces"""
+    return Spec(hipabi.MEASURE_AREA, (), (0.0, 0.0, 0.0), _parts(parts, 'measure.area'))
+
+
+def extent(axis):
+    """max - min of axis . p over all vertices (axis is not normalised)"""
+    return Spec(hipabi.MEASURE_EXTENT, (), _direction(axis, 'measure.extent'), None)
+
+
+def girth(anchor, normal, parts=None):
+    """length of the section of the selected faces with the plane through `anchor` with normal `normal`"""
+    return Spec(hipabi.MEASURE_GIRTH, (_anchor(anchor, 'measure.girth'),), _direction(normal, 'measure.girth'), _parts(parts, 'measure.girth'))
+
+
+def path(*anchors):
+    """length of the polyline through two to four anchors"""
+    if not 2 <= len(anchors) <= 4:
+        raise ValueError('measure.path: two to four anchors (got %d)' % len(anchors))
+    return Spec(hipabi.MEASURE_PATH, tuple(_anchor(a, 'measure.path') for a in anchors), (0.0, 0.0, 0.0), None)
+
+
+def default_measurements():
+    """The default set, anchored at SMPL's public joint numbering (0 pelvis, 1 / 2 hips, 3 spine1, 4 / 5 knees, 7 / 8 ankles, 9 spine3, 16 / 17
+    shoulders, 18 / 19 elbows, 20 / 21 wrists) and this package's part labels, for T-pose bodies (y up, arms along x):
+
+        height               extent along y
+        volume, surface_area the whole mesh
+        chest_girth          plane through joint 9, normal y, torso          waist_girth   joint 3          hip_girth   joint 0
+        thigh_girth_l / _r   plane with normal y through the KNEE joint (4 / 5), leg parts: the leg's section at the knee's height.  Joints 1 / 2
+                             (the hip joints) lie at the top of the leg part, where the section runs into the torso boundary; the knee is the
+                             joint that lies inside the leg part on every body, so the section is a closed loop of leg faces
+        upper_arm_girth_l/_r plane with normal x through the elbow joint (18 / 19), arm parts
+        arm_length_l / _r    paths 16-18-20 and 17-19-21            leg_length_l / _r   paths 1-4-7 and 2-5-8
+        shoulder_breadth     path 16-17
+
+    These positions are UNTUNED on the real model: no SMPL file was available when they were chosen, only the synthetic stand-in, whose
+    triangle soup is not a body surface.  Check them on your model (and move a plane along a limb with your own specs) before relying on
+    absolute numbers.  The fit defaults carry the same warning."""
+    j = lambda k: ('joint', k)
+    y, x = (0.0, 1.0, 0.0), (1.0, 0.0, 0.0)
+    return collections.OrderedDict([
+        ('height', extent(y)), ('volume', volume()), ('surface_area', area()),
+        ('chest_girth', girth(j(9), y, parts=(6,))), ('waist_girth', girth(j(3), y, parts=(6,))), ('hip_girth', girth(j(0), y, parts=(6,))),
+        ('thigh_girth_l', girth(j(4), y, parts=(4,))), ('thigh_girth_r', girth(j(5), y, parts=(5,))),
+        ('upper_arm_girth_l', girth(j(18), x, parts=(1,))), ('upper_arm_girth_r', girth(j(19), x, parts=(2,))),
+        ('arm_length_l', path(j(16), j(18), j(20))), ('arm_length_r', path(j(17), j(19), j(21))),
+        ('leg_length_l', path(j(1), j(4), j(7))), ('leg_length_r', path(j(2), j(5), j(8))),
+        ('shoulder_breadth', path(j(16), j(17)))])
+
+
+def measure_structs(specs, nverts):
+    """-> (hipabi.MeasureStruct array, number of points the specs read): ('joint', j) anchors resolve to nverts + j"""
+    arr = (hipabi.MeasureStruct * len(specs))()
+    n_points = 0
+    for q, s in zip(arr, specs):
+        q.kind = s.kind
+        q.anchor[:] = [-1, -1, -1, -1]
+        for i, a in enumerate(s.anchors):
+            if isinstance(a, tuple):
+                q.anchor[i] = nverts + a[1]
+                n_points = max(n_points, a[1] + 1)
+            else:
+                q.anchor[i] = a
+        q.dir[:] = s.direction
+        q.part_mask = sum(1 << p for p in s.parts) if s.parts else 0
+    return arr, n_points
+
+
+class BodyMeasurer(nn.Module):
+    """Measures a batch of meshes of one topology (see the module docstring).  faces [F,3] and face_parts [F] (None: no spec may name parts) are
+    held as buffers; faces=None loads config.SMPL_FACES_PATH, and then the part table from the reference's texture files, as NMRRenderer does.
+    measurements=None: default_measurements()."""
+
+    def __init__(self, faces=None, face_parts=None, measurements=None):
+        super().__init__()
+        name = 'BodyMeasurer'
+        if faces is None:
+            if not os.path.isfile(config.SMPL_FACES_PATH):
+                raise RuntimeError('%s: %s not found; pass faces= (e.g. from synthetic_smpl_model()) or use from_smpl' % (name, config.SMPL_FACES_PATH))
+            faces = np.load(config.SMPL_FACES_PATH)
+            if face_parts is None and os.path.isfile(config.VERTEX_TEXTURE_PATH) and os.path.isfile(config.CUBE_PARTS_PATH):
+                from .nmr_renderer import face_parts_from_texture
+                face_parts = face_parts_from_texture(np.load(config.VERTEX_TEXTURE_PATH), np.load(config.CUBE_PARTS_PATH))
+        as_numpy = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        faces = np.ascontiguousarray(as_numpy(faces).astype(np.int32))
+        if faces.ndim != 2 or faces.shape[1] != 3:
+            raise RuntimeError('%s: faces must be [F,3] (got %s)' % (name, faces.shape))
+        self.register_buffer('faces', torch.from_numpy(faces))
+        if face_parts is not None:
+            face_parts = np.ascontiguousarray(as_numpy(face_parts).astype(np.uint8))
+            if face_parts.shape != (faces.shape[0],):
+                raise RuntimeError('%s: face_parts must be [%d] (got %s)' % (name, faces.shape[0], face_parts.shape))
+            face_parts = torch.from_numpy(face_parts)
+        self.register_buffer('face_parts', face_parts)
+        measurements = default_measurements() if measurements is None else measurements
+        items = list(measurements.items()) if hasattr(measurements, 'items') else [tuple(m) for m in measurements]
+        if not 1 <= len(items) <= hipabi.MEASURE_MAX:
+            raise RuntimeError('%s: 1 to %d measurements (got %d)' % (name, hipabi.MEASURE_MAX, len(items)))
+        self.names = tuple(str(n) for n, _ in items)
+        self.specs = tuple(s for _, s in items)
+        if len(set(self.names)) != len(self.names) or 'values' in self.names:
+            raise RuntimeError("%s: measurement names must be distinct and none may be 'values' (got %r)" % (name, self.names))
+        for n, s in items:
+            if not isinstance(s, Spec):
+                raise RuntimeError('%s: measurement %r is not a spec of measure.volume / area / extent / girth / path (got %r)' % (name, n, s))
+            if s.parts and face_parts is None:
+                raise RuntimeError('%s: measurement %r selects parts %r but no face_parts table was given' % (name, n, s.parts))
+            if s.kind in (hipabi.MEASURE_VOLUME, hipabi.MEASURE_AREA, hipabi.MEASURE_GIRTH) and faces.shape[0] == 0:
+                raise RuntimeError('%s: measurement %r reads faces but the face table is empty' % (name, n))
+        self.needs_joints = max([a[1] + 1 for s in self.specs for a in s.anchors if isinstance(a, tuple)] or [0])
+        self._structs = {}
+
+    @classmethod
+    def from_smpl(cls, smpl, measurements=None):
+        """the face and part tables of an SMPL module (its `.faces` / `.face_parts`: the model file's, or the synthetic model's)"""
+        if getattr(smpl, 'faces', None) is None:
+            raise RuntimeError('BodyMeasurer.from_smpl: the SMPL model carries no faces; pass faces= (and face_parts=) to BodyMeasurer')
+        return cls(smpl.faces, getattr(smpl, 'face_parts', None), measurements)
+
+    @hipabi.on_tensor_device
+    def measure_arrays(self, vertices, joints=None):
+        """vertices [B,N,3], joints None or [B,J,3] (fp32 GPU) -> values [B,M] float32.  Never synchronises; runs on the current stream;
+        capturable."""
+        name = 'BodyMeasurer'
+        hipabi.require_gpu_tensor(vertices, 'vertices', torch.float32)
+        hipabi.require_gpu_tensor(self.faces, name + ' buffers (call .to(device))', torch.int32)
+        if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1:
+            raise RuntimeError('%s: expected vertices [B,N,3], got %s' % (name, tuple(vertices.shape)))
+        B, N = vertices.shape[0], vertices.shape[1]
+        points = None
+        if self.needs_joints:
+            if joints is None:
+                raise RuntimeError("%s: the measurements %r are anchored at joints: pass joints [B,J,3] with J >= %d"
+                                   % (name, [n for n, s in zip(self.names, self.specs) if any(isinstance(a, tuple) for a in s.anchors)], self.needs_joints))
+            hipabi.require_gpu_tensor(joints, 'joints', torch.float32)
+            if joints.dim() != 3 or joints.shape[0] != B or joints.shape[2] != 3 or joints.shape[1] < self.needs_joints:
+                raise RuntimeError('%s: joints must be [%d,J,3] with J >= %d, got %s' % (name, B, self.needs_joints, tuple(joints.shape)))
+            points = joints.detach()[:, :self.needs_joints].contiguous()           # (the library takes at most 64 points: the leading joints that are read)
+        for n, s in zip(self.names, self.specs):
+            for a in s.anchors:
+                if not isinstance(a, tuple) and a >= N:
+                    raise RuntimeError('%s: measurement %r is anchored at vertex %d, the mesh has %d' % (name, n, a, N))
+        if N not in self._structs:
+            self._structs[N] = measure_structs(self.specs, N)
+        arr, n_points = self._structs[N]
+        vertices = vertices.detach().contiguous()
+        L = hipabi.lib()
+        M, F = len(self.specs), self.faces.shape[0]
+        out = torch.empty(B, M, device=vertices.device, dtype=torch.float32)
+        ws = torch.empty(L.straps_measure_workspace_bytes(B, N, F, M) // 8, device=vertices.device, dtype=torch.float64)
+        hipabi.check(L.straps_measure_mesh(hipabi.ptr(vertices), hipabi.ptr(points), hipabi.ptr(self.faces) if F else None, hipabi.ptr(self.face_parts), arr,
+                                           hipabi.ptr(out), hipabi.ptr(ws), B, N, n_points, F, M, hipabi.stream_ptr()), 'straps_measure_mesh')
+        return out
+
+    def forward(self, vertices, joints=None):
+        """-> {'values': [B,M] float32, name: [B] (a view of its column), ...} in the order of `self.names`"""
+        values = self.measure_arrays(vertices, joints)
+        res = {'values': values}
+        for i, n in enumerate(self.names):
+            res[n] = values[:, i]
+        return res

@@ -10,6 +10,7 @@ These are the PREDICT-side semantics, not the training-side ones of image_utils.
 is not clamped to the frame (what sticks out reads as zero, and the joints are shifted by the unclamped corner), and the heat maps are
 the numpy ones (float64 joints truncated to int16, a float64 Gaussian).  The detectors, pad_to_square and the resize of the RGB image are
 not part of this package; of the visualisation, the two rendered pictures of predict_3D.py:169-178 are (`Predictor.render`).
+`Predictor.measure` turns the predicted T-pose body into height, volume, girths and limb lengths (measure.py).
 """
 import numpy as np
 import torch
@@ -173,3 +174,15 @@ class Predictor:
         with torch.no_grad():
             return {'rend': renderer(verts, out['cam_wp'], background=images),
                     'reposed': renderer(out['reposed_vertices'], cam.expand(B, 3).contiguous(), rotation=rx180)}
+
+    @hipabi.on_tensor_device
+    def measure(self, out, measurer):
+        """body measurements of the prediction: `out` a result of __call__ or refine, `measurer` a measure.BodyMeasurer on the same GPU.  Measures
+        out['reposed_vertices'] -- the predicted shape in the T-pose -- with the T-pose joints as anchor points: one extra SMPL forward on
+        out['shape'] with identity rotations (its vertices are the reposed vertices again and are dropped).  `out` is not changed.
+        -> {'values': [B,M] float32, name: [B], ...} (BodyMeasurer.forward).  Never synchronises; capturable after a warm-up call."""
+        with torch.no_grad():
+            shape = out['shape'].contiguous()
+            B = shape.shape[0]
+            _, joints = self.smpl.forward_arrays(shape, self._identity_rotmats(B, shape.device))
+            return measurer(out['reposed_vertices'], joints)
