@@ -8,6 +8,8 @@ the tables need -- so that every case can say which instantiation and which epil
     pick_tile_x3f / stream_bn / x3f_route                                                  the fp32-operand 1x1 route
     wgrad3_plan / wgrad_x3_route / wgrad_x3_block / wgrad_plan                             weight gradients on planes and on fp32 tensors
     wgrad_x3f_block / wgrad_x3f_plan                                                       weight gradient of the fp32-operand route
+    pick_tile_bf16 / bf16_refusal / bf16_route / bf16_nchunks                              the single-product bf16 inference route (conv_bf16.hip;
+                                                                                           the cases of tests/test_gpu_conv_bf16_edges.py)
 
 tests/test_conv_cases_cpu.py holds the restatement to everything the built library reveals without a launch (the block-count, workspace and route
 queries) for every case, and asserts that the tables together reach every instantiation the product library can dispatch to (REQUIRED below; the
@@ -20,6 +22,7 @@ An instantiation is named by a tuple:
     ('x3f_stream', bn, epi, abn) conv1x1_stream_kernel, 256 (resident weights) / 128 / 64 wide
     ('wgrad3_x3', cp)           conv_wgrad3x3_x3_kernel with 32- or 64-pixel chunks;  ('wgrad3_f32',) conv_wgrad3x3_kernel
     ('wgrad_x3', bco, bci)      conv_wgrad_x3_kernel;  ('wgrad_f32', b) conv_wgrad_kernel<b, b>;  ('wgrad_x3f', bco, bci, abn) conv_wgrad_x3f_kernel
+    ('bf16', cfg)               tile configuration cfg (1-10) of conv_bf16.hip: conv_igemm_x3_kernel / conv_igemm_x3h_kernel with PL chunks per stage, EPI = 3
 """
 from collections import namedtuple
 
@@ -415,6 +418,100 @@ def last_split_state(pl):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
+# the single-product bf16 inference route (conv_bf16.hip): the PL != 0 instantiations of conv_x3_kernels.h with the EPI = 3 plane epilogue
+
+BF16_BM = {1: 128, 2: 128, 3: 64, 4: 256, 5: 256, 6: 128, 7: 128, 8: 128, 9: 128, 10: 128}
+BF16_BN = {1: 128, 2: 64, 3: 64, 4: 128, 5: 128, 6: 128, 7: 128, 8: 64, 9: 128, 10: 64}
+BF16_PL = {1: 2, 2: 2, 3: 2, 4: 2, 5: 2, 6: 4, 7: 2, 8: 1, 9: 2, 10: 2}          # 32-channel K chunks per stage
+BF16_NST = {1: 3, 2: 3, 3: 3, 4: 2, 5: 2, 6: 2, 7: 3, 8: 3, 9: 3, 10: 2}         # stages of the operand ring
+BF16_PIPE = (5, 7)                                                              # the software-pipelined loop: its prologue issues NST chunks
+BF16_HALO = {9: 208, 10: 272}                                                   # the halo-patch tiles and their slot limits
+BF16_TILES = tuple(sorted(BF16_BM))
+# what cfg_refusal says (the texts of straps_last_error(), as far as a test needs to tell them apart)
+BF16_WHY_N = "cout is not a multiple of the tile's N extent"
+BF16_WHY_K = 'the four-chunk stage needs cin % 128 == 0'
+BF16_WHY_HALO = {9: 'the halo-patch tile needs a 3x3 / stride-1 layer whose patch fits 208 slots', 10: 'the halo-patch tile needs a 3x3 / stride-1 layer whose patch fits 272 slots'}
+
+
+def pick_tile_bf16(M, cout):
+    """conv_bf16.hip's pick_tile_bf16: the configuration tile_cfg = 0 takes"""
+    t128 = ((M + 127) // 128) * (cout // 128)
+    if cout % 128 != 0 or t128 < 256:
+        return 3
+    return 1 if t128 < 512 else 5
+
+
+def bf16_refusal(p, cfg):
+    """conv_bf16.hip's cfg_refusal -> None (the problem admits the configuration) or the reason"""
+    if cfg not in BF16_BM:
+        return 'unknown tile configuration'
+    if p.Cout % BF16_BN[cfg] != 0:
+        return BF16_WHY_N
+    if cfg == 6 and p.Cin % 128 != 0:
+        return BF16_WHY_K
+    if cfg in BF16_HALO and not 0 < halo_patch_slots(p) <= BF16_HALO[cfg]:
+        return BF16_WHY_HALO[cfg]
+    return None
+
+
+def bf16_route(p, cfg):
+    """-> ('bf16', cfg): the instantiation dispatch_bf16 launches for an ADMITTED configuration (cfg 0: the automatic rule's)"""
+    if cfg == 0:
+        cfg = pick_tile_bf16(p.cls[0].M, p.Cout)
+    assert bf16_refusal(p, cfg) is None, (p, cfg)
+    return ('bf16', cfg)
+
+
+def bf16_nchunks(p, cfg):
+    """stages of the K loop: taps x (32-channel chunks / PL) -- the kernels' nchunks / nsteps"""
+    return p.cls[0].ntaps * ((p.Cin // 32) // BF16_PL[cfg])
+
+
+def bf16_problem(c):
+    B, H, W, ci, co, k, s = c[:7]
+    return fwd_problem(B, H, W, ci, co, k, s, k // 2)
+
+
+# A bf16 case is (B, H, W, Cin, Cout, k, stride), pad = k // 2.  BF16_EXPLICIT: every case runs under EVERY configuration 1..10 -- launched where
+# bf16_refusal admits it, refused with the stated reason elsewhere.  BF16_AUTO: tile_cfg = 0.
+BF16_KLOOP = [(1, 5, 13, ci, 128, 1, 1) for ci in (64, 128, 192, 256, 384)] + \
+             [(2, 9, 9, 64, 128, 3, 1), (2, 9, 9, 128, 128, 3, 1)]      # 3x3: the tap rolls over every stage (cin 64, PL = 2) / every second one
+# M = 1, BM - 1, BM, BM + 1 and a ragged two-tile M for BM = 64, 128, 256 (1x1, cin 64): M = 1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 385
+BF16_M_EDGES = [(1, 1, 1, 64, 64, 1, 1)] + [(1, h, w, 64, 128, 1, 1) for (h, w) in ((1, 1), (1, 63), (8, 8), (65, 1), (1, 127), (1, 128), (1, 129), (3, 85), (16, 16), (257, 1), (5, 77))]
+# 3x3 whose taps are all padding but the centre (H = W = 1) / but the centre row (H = 1): every PL slot of a padding pixel reads the zero constant
+BF16_PADDING = [(1, 1, 1, 64, 128, 3, 1), (1, 1, 3, 64, 128, 3, 1), (1, 1, 1, 128, 128, 3, 1), (1, 1, 3, 128, 128, 3, 1)]
+BF16_STRIDE2 = [(3, 7, 9, 64, 128, 3, 2), (2, 7, 5, 128, 64, 1, 2)]
+BF16_N_EDGES = [(1, 5, 13, 64, 64, 1, 1), (1, 5, 13, 64, 192, 1, 1), (1, 5, 13, 64, 320, 1, 1), (2, 9, 9, 64, 192, 3, 1)]
+# halo tiles: a patch of two images (200 slots), one image per tile (180), two tiles per image (180), four-row tiles (204); 264 slots: cfg 10 alone
+BF16_HALO_RUN = [(b, h, w, ci, 128, 3, 1) for (b, h, w) in ((2, 8, 8), (1, 16, 8), (1, 16, 16), (1, 32, 32)) for ci in (64, 128)] + \
+                [(1, 64, 64, 64, 64, 3, 1), (1, 64, 64, 64, 128, 3, 1)]
+# ... and refused by both: 288 slots, a stride-2 layer, a 1x1 layer, M % 128 != 0
+BF16_HALO_REFUSED = [(8, 4, 4, 64, 128, 3, 1), (2, 16, 16, 64, 128, 3, 2), (2, 8, 8, 64, 128, 1, 1), (3, 8, 8, 64, 128, 3, 1)]
+# the ragged geometries of tests/test_gpu_conv_bf16.py::test_ragged_tiles_and_output_forms (the first is in BF16_STRIDE2)
+BF16_OLD_RAGGED = [(2, 5, 11, 128, 64, 1, 1), (1, 9, 9, 256, 128, 3, 1), (5, 8, 8, 512, 512, 3, 1)]
+BF16_EXPLICIT = BF16_KLOOP + BF16_M_EDGES + BF16_PADDING + BF16_STRIDE2 + BF16_N_EDGES + BF16_HALO_RUN + BF16_HALO_REFUSED + BF16_OLD_RAGGED
+
+# the automatic rule reads M and cout only: t128 = 255 / 256 / 511 / 512 -> cfg 3 / 1 / 1 / 5; 64 and 192 output channels stay on cfg 3 at 512 M tiles
+# (cout = 192: t128 = 512, the `cout % 128` test comes first)
+BF16_AUTO = [(1, 255, 128, 64, 128, 1, 1), (1, 256, 128, 64, 128, 1, 1), (1, 511, 128, 64, 128, 1, 1), (1, 512, 128, 64, 128, 1, 1),
+             (1, 512, 128, 64, 64, 1, 1), (1, 512, 128, 64, 192, 1, 1)]
+BF16_AUTO_WANT = [3, 1, 1, 5, 3, 3]
+
+# a body alone equals its rows in the batch, bit for bit: (case, configuration) -- one 128-row tile spans all three images; a halo patch of two images
+BF16_BATCH = [((3, 5, 5, 128, 128, 3, 1), 1), ((3, 5, 5, 128, 128, 3, 1), 7), ((2, 8, 8, 64, 128, 3, 1), 9)]
+
+# split and pack: (rows, c) of straps_split_bf16_cm, (cout, cin, kh, kw) of straps_pack_conv_weight_bf16.  Both kernels run at most 16384 workgroups of
+# 256 threads; split1_cm_kernel handles four values per thread, pack_w_bf16_kernel one
+BF16_GRID_CAP = 16384 * 256
+BF16_SPLIT = [(1, 32), (1, 64), (3, 96), (257, 32), (65536, 256), (65540, 256)]          # the last two: just under (exactly at) and just past the cap
+BF16_PACK = [(64, 32, 1, 1), (64, 64, 3, 3), (192, 96, 3, 3), (1, 32, 3, 3), (64, 64, 1, 3), (64, 64, 3, 1), (512, 1024, 3, 3)]
+
+
+def bf16_case_id(c):
+    return 'B%d_%dx%d_%dto%d_k%ds%d' % tuple(c[:7])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
 # the case tables.  A convolution case is (B, H, W, Cin, Cout, k, stride, tile_cfg): H x W is the INPUT map of the forward convolution (= the map of
 # dx for a data gradient), Cin -> Cout its channels; pad = 1 for 3x3, 0 for 1x1.
 
@@ -641,6 +738,13 @@ def reached():
         add(wgrad_plan(*c, pad_of(c[5]), planes=False).inst, 'wgrad_f32:B%d_%dx%d_%dto%d_k%ds%d' % c)
     for c in WGRAD_X3F:
         add(wgrad_x3f_plan(*c).inst, 'wgrad_x3f:B%d_%dx%d_%dto%d_s%d_bn%d' % c)
+    for c in BF16_EXPLICIT:          # (tests/test_gpu_conv_bf16_edges.py: every admitted configuration of every case)
+        p = bf16_problem(c)
+        for cfg in BF16_TILES:
+            if bf16_refusal(p, cfg) is None:
+                add(bf16_route(p, cfg), 'bf16:' + bf16_case_id(c))
+    for c in BF16_AUTO:
+        add(bf16_route(bf16_problem(c), 0), 'bf16:' + bf16_case_id(c) + '_cfg0')
     return got
 
 
@@ -660,7 +764,8 @@ REQUIRED = (
     [('x3f_stream', bn, e, a) for bn in (256, 128, 64) for (e, a) in ((1, False), (1, True), (2, False))] +
     [('wgrad3_x3', 32), ('wgrad3_x3', 64), ('wgrad3_f32',), ('wgrad_f32', 64), ('wgrad_f32', 128)] +
     [('wgrad_x3', o, i) for (o, i) in ((256, 128), (128, 64), (64, 128), (128, 128), (64, 64))] +
-    [('wgrad_x3f', o, i, a) for (o, i) in ((256, 64), (64, 256), (256, 128), (128, 256), (128, 128), (64, 64)) for a in (False, True)]
+    [('wgrad_x3f', o, i, a) for (o, i) in ((256, 64), (64, 256), (256, 128), (128, 256), (128, 128), (64, 64)) for a in (False, True)] +
+    [('bf16', c) for c in BF16_TILES]
 )
 
 # instantiations the library holds that no 1x1 / 3x3 layer reaches (listed in DESIGN.md as well); the tables do not invent a route to them

@@ -1,7 +1,9 @@
 """CPU: tests/conv_cases.py -- the Python restatement of the convolution family's dispatch -- held to everything the built library reveals without a
 launch (block counts, workspace bytes, route queries; no compute calls -- there is no GPU here), the conditions the case tables of
 tests/test_gpu_conv_edges.py are named for, and the coverage statement: the tables together reach every instantiation the product library can
-dispatch to.  A later change of a size rule that moves a case off its kernel fails here instead of thinning the coverage quietly."""
+dispatch to.  A later change of a size rule that moves a case off its kernel fails here instead of thinning the coverage quietly.  The same for the
+single-product bf16 inference route (csrc/conv_bf16.hip) and the tables of tests/test_gpu_conv_bf16_edges.py: the automatic rule against
+straps_conv_bf16_tile_choice, every stated refusal against the entry point (refused before any launch), the ten configurations and the edge classes."""
 import ctypes as C
 import itertools
 
@@ -306,3 +308,139 @@ def test_weight_gradient_tables_hold_the_plans_they_are_named_for():
     assert set(fb) == {(256, 64), (64, 256), (256, 128), (128, 256), (128, 128), (64, 64)} and all({1, 31, 33, 129} <= m for m in fb.values())
     assert 'empty' in {K.last_split_state(K.wgrad_x3f_plan(*c)) for c in K.WGRAD_X3F}
     assert {K.wgrad_plan(*c, K.pad_of(c[5]), planes=False).inst for c in K.WGRAD_F32} == {('wgrad3_f32',), ('wgrad_f32', 64), ('wgrad_f32', 128)}
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------
+# the single-product bf16 inference route (csrc/conv_bf16.hip): the tables of tests/test_gpu_conv_bf16_edges.py
+
+def _bf16_geo(c):
+    B, H, W, ci, co, k, s = c
+    return (B, H, W, ci, co, k, k, s, k // 2)
+
+
+def test_bf16_tile_choice_is_the_restated_rule(lib):
+    """straps_conv_bf16_tile_choice == pick_tile_bf16 for every case of both tables and on a grid around the rule's thresholds (255 / 256 / 511 /
+    512 tile equivalents, M one short of and one past a multiple of 128, cout % 128); the automatic cases land on the configurations they are named for"""
+    for c in K.BF16_EXPLICIT + K.BF16_AUTO:
+        p = K.bf16_problem(c)
+        assert lib.straps_conv_bf16_tile_choice(*_bf16_geo(c)) == K.pick_tile_bf16(p.cls[0].M, p.Cout), c
+    assert [K.bf16_route(K.bf16_problem(c), 0)[1] for c in K.BF16_AUTO] == K.BF16_AUTO_WANT
+    assert [lib.straps_conv_bf16_tile_choice(*_bf16_geo(c)) for c in K.BF16_AUTO] == K.BF16_AUTO_WANT
+    n = 0
+    for M, co, (k, s) in itertools.product((1, 127, 128, 129, 255 * 128, 255 * 128 + 1, 256 * 128 - 1, 256 * 128, 256 * 128 + 1, 511 * 128, 511 * 128 + 1, 512 * 128, 1024 * 128),
+                                           (64, 128, 192, 256, 320, 512), ((1, 1), (3, 1))):
+        for (B, H, W) in ((1, 1, M), (1, M, 1)) + (((M // 128, 16, 8),) if M % 128 == 0 else ()):
+            assert lib.straps_conv_bf16_tile_choice(B, H, W, 64, co, k, k, s, k // 2) == K.pick_tile_bf16(M, co), (B, H, W, co, k)
+            n += 1
+    assert n > 300
+    # every configuration the rule can return admits every geometry it returns it for (cfg 3: cout % 64, cfg 1 / 5: only at cout % 128 == 0)
+    for c in K.BF16_EXPLICIT + K.BF16_AUTO:
+        p = K.bf16_problem(c)
+        assert K.bf16_refusal(p, K.pick_tile_bf16(p.cls[0].M, p.Cout)) is None
+
+
+V = C.c_void_p(8192)          # a non-null, 16-byte aligned address that is never dereferenced: the calls below are refused before any launch
+
+
+def test_bf16_refusals_are_the_restated_ones(lib):
+    """every (case, configuration) the restatement of cfg_refusal refuses is refused by straps_conv_fwd_bf16 with that reason -- the call returns before
+    anything is launched (the operand pointers are no memory at all).  That the admitted ones run is asserted on the GPU."""
+    n = 0
+    why_seen = set()
+    for c in K.BF16_EXPLICIT:
+        p = K.bf16_problem(c)
+        for cfg in K.BF16_TILES:
+            why = K.bf16_refusal(p, cfg)
+            if why is None:
+                continue
+            rc = lib.straps_conv_fwd_bf16(V, V, None, None, None, 0, V, V, *_bf16_geo(c), cfg, None)
+            assert rc != 0 and why in lib.straps_last_error().decode(), (c, cfg, rc, lib.straps_last_error())
+            assert ('tile_cfg %d:' % cfg) in lib.straps_last_error().decode()
+            why_seen.add(why)
+            n += 1
+    assert why_seen == {K.BF16_WHY_N, K.BF16_WHY_K, K.BF16_WHY_HALO[9], K.BF16_WHY_HALO[10]} and n > 100
+    assert K.bf16_refusal(K.bf16_problem(K.BF16_EXPLICIT[0]), 11) == 'unknown tile configuration'
+
+
+def test_bf16_tables_reach_all_ten_configurations_and_hold_every_edge_class():
+    """asserted on the tables, so that a later edit cannot drop an edge quietly"""
+    got = K.reached()
+    for cfg in K.BF16_TILES:
+        assert ('bf16', cfg) in got and ('bf16', cfg) in K.REQUIRED
+    assert len(set(K.BF16_EXPLICIT)) == len(K.BF16_EXPLICIT) and len(set(K.BF16_AUTO)) == len(K.BF16_AUTO)
+    ran = {}          # cfg -> [(case, problem)] of the launches
+    refused = {}      # cfg -> [(case, problem, reason)]
+    for c in K.BF16_EXPLICIT:
+        p = K.bf16_problem(c)
+        for cfg in K.BF16_TILES:
+            why = K.bf16_refusal(p, cfg)
+            (ran if why is None else refused).setdefault(cfg, []).append((c, p) if why is None else (c, p, why))
+
+    # ---- K-loop length: 1x1 layers with 1, 2, 3, 4 stages where PL allows (PL = 1: 2, 4, 6, 8; PL = 4: 1, 2, 3), on every non-halo configuration:
+    # fewer chunks than the prologue issues (NST - 1; the pipelined loops NST), exactly as many, and one more
+    for cfg in (1, 2, 3, 4, 5, 6, 7, 8):
+        n1 = {K.bf16_nchunks(p, cfg) for c, p in ran[cfg] if c[5] == 1}
+        assert n1 >= {1: {2, 4, 6, 8}, 4: {1, 2, 3}}.get(K.BF16_PL[cfg], {1, 2, 3, 4}), (cfg, n1)
+        pro = K.BF16_NST[cfg] if cfg in K.BF16_PIPE else K.BF16_NST[cfg] - 1
+        if K.BF16_PL[cfg] != 1:
+            assert {pro - 1, pro, pro + 1} - {0} <= n1, (cfg, pro, n1)
+        # 3x3 with the fewest stages per tap the configuration can have (one: the tap rolls over at every stage; PL = 1: two -- cin % 64) and with more
+        per_tap = {(p.Cin // 32) // K.BF16_PL[cfg] for c, p in ran[cfg] if c[5] == 3}
+        least = 2 if K.BF16_PL[cfg] == 1 else 1
+        assert least in per_tap and any(x > least for x in per_tap), (cfg, per_tap)
+    assert {c[3] for c, p, why in refused[6] if why == K.BF16_WHY_K and c[5] == 1} >= {64, 192}
+    assert (2, 9, 9, 64, 128, 3, 1) in K.BF16_EXPLICIT and (2, 9, 9, 128, 128, 3, 1) in K.BF16_EXPLICIT
+
+    # ---- M edges per row tile: 1, BM - 1, BM, BM + 1, a ragged two-tile M -- on every non-halo configuration of that BM (cfg 6: by its 3x3 / cin 128 cases
+    # and M = 1 only -- the 1x1 edges are cin 64)
+    for cfg in (1, 2, 3, 4, 5, 7, 8):
+        bm = K.BF16_BM[cfg]
+        ms = {p.cls[0].M for c, p in ran[cfg]}
+        assert {1, bm - 1, bm, bm + 1} <= ms and any(bm + 1 < m < 2 * bm and m % bm for m in ms), (cfg, sorted(ms))
+    assert 1 in {p.cls[0].M for c, p in ran[6]} and any(p.cls[0].M % 128 for c, p in ran[6])
+    assert (1, 1, 1, 64, 64, 1, 1) in K.BF16_EXPLICIT
+    # ---- padding pixels: 3x3 at H = W = 1 and H = 1, W = 3, at PL = 2 and (cin 128) PL = 4
+    for hw in ((1, 1), (1, 3)):
+        for ci in (64, 128):
+            assert (1,) + hw + (ci, 128, 3, 1) in K.BF16_EXPLICIT
+    # ---- stride 2 on odd extents, 3x3 and 1x1
+    assert (3, 7, 9, 64, 128, 3, 2) in K.BF16_EXPLICIT and (2, 7, 5, 128, 64, 1, 2) in K.BF16_EXPLICIT
+    # ---- N edges: cout 64, 128, 192, 320; 192 and 320 run on the 64-wide tiles only, the 128-wide ones refuse them
+    assert {c[4] for c in K.BF16_EXPLICIT} >= {64, 128, 192, 320}
+    for co in (192, 320):
+        for cfg in K.BF16_TILES:
+            wide = K.BF16_BN[cfg] == 128
+            assert any(c[4] == co and why == K.BF16_WHY_N for c, p, why in refused.get(cfg, [])) == wide, (co, cfg)
+            if not wide and cfg not in K.BF16_HALO:
+                assert any(c[4] == co for c, p in ran[cfg]), (co, cfg)
+    # ---- halo tiles: the slot counts the cases are named for
+    slots = {c: K.halo_patch_slots(K.bf16_problem(c)) for c in K.BF16_HALO_RUN + K.BF16_HALO_REFUSED}
+    for ci in (64, 128):
+        assert [slots[(b, h, w, ci, 128, 3, 1)] for (b, h, w) in ((2, 8, 8), (1, 16, 8), (1, 16, 16), (1, 32, 32))] == [200, 180, 180, 204]
+        for (b, h, w) in ((2, 8, 8), (1, 16, 8), (1, 16, 16), (1, 32, 32)):
+            assert ((b, h, w, ci, 128, 3, 1), K.bf16_problem((b, h, w, ci, 128, 3, 1))) in ran[9] and ((b, h, w, ci, 128, 3, 1), K.bf16_problem((b, h, w, ci, 128, 3, 1))) in ran[10]
+    assert slots[(1, 64, 64, 64, 64, 3, 1)] == slots[(1, 64, 64, 64, 128, 3, 1)] == 264          # cfg 10 alone
+    for c in ((1, 64, 64, 64, 64, 3, 1), (1, 64, 64, 64, 128, 3, 1)):
+        assert K.bf16_refusal(K.bf16_problem(c), 10) is None and K.bf16_refusal(K.bf16_problem(c), 9) is not None
+    assert K.bf16_refusal(K.bf16_problem((1, 64, 64, 64, 128, 3, 1)), 9) == K.BF16_WHY_HALO[9]      # (by the slot limit, not by cout)
+    assert slots[(8, 4, 4, 64, 128, 3, 1)] == 288
+    kinds = set()
+    for c in K.BF16_HALO_REFUSED:
+        p = K.bf16_problem(c)
+        assert K.bf16_refusal(p, 9) == K.BF16_WHY_HALO[9] and K.bf16_refusal(p, 10) == K.BF16_WHY_HALO[10], c
+        kinds.add('slots' if slots[c] > 272 else 'stride' if c[6] == 2 else '1x1' if c[5] == 1 else 'ragged' if p.cls[0].M % 128 else '?')
+    assert kinds == {'slots', 'stride', '1x1', 'ragged'}
+    # ---- the automatic rule: t128 = 255 / 256 / 511 / 512 at cout 128; 64 and 192 output channels at 512 M tiles
+    t = [(-(-K.bf16_problem(c).cls[0].M // 128) * (c[4] // 128), c[4]) for c in K.BF16_AUTO]
+    assert t[:4] == [(255, 128), (256, 128), (511, 128), (512, 128)] and (0, 64) in t and (512, 192) in t
+    assert all(-(-K.bf16_problem(c).cls[0].M // 128) >= 512 for c in K.BF16_AUTO if c[4] != 128)
+    # ---- batch independence: a 128-row tile that spans three images; a halo patch of two images
+    assert ((3, 5, 5, 128, 128, 3, 1), 1) in K.BF16_BATCH and ((2, 8, 8, 64, 128, 3, 1), 9) in K.BF16_BATCH
+    for c, cfg in K.BF16_BATCH:
+        assert K.bf16_refusal(K.bf16_problem(c), cfg) is None and c[1] * c[2] < K.BF16_BM[cfg]
+    # ---- split and pack: both sides of the grid cap (the second trip of the grid-stride loop), the small shapes, the 1x3 and 3x1 filters
+    n4 = [r * c // 4 for r, c in K.BF16_SPLIT]
+    assert any(n == K.BF16_GRID_CAP for n in n4) and any(K.BF16_GRID_CAP < n <= K.BF16_GRID_CAP + 4096 for n in n4)
+    assert {(1, 32), (1, 64), (3, 96), (257, 32)} <= set(K.BF16_SPLIT)
+    assert any(o * ci * kh * kw > K.BF16_GRID_CAP for o, ci, kh, kw in K.BF16_PACK)
+    assert {(64, 32, 1, 1), (64, 64, 3, 3), (192, 96, 3, 3), (1, 32, 3, 3), (64, 64, 1, 3), (64, 64, 3, 1)} <= set(K.BF16_PACK)

@@ -1,7 +1,8 @@
 """GPU: the single-product bf16 convolution (straps_conv_fwd_bf16, csrc/conv_bf16.hip) against its EXACT model -- a float64 convolution of
 rn_bf16(x) and rn_bf16(w) with the epilogue in float64.  The products are exact in the fp32 accumulator, so only the summation order
 differs from the model: the bars are the fp32 chain's of tests/test_gpu_conv_x3.py (2e-5 abs + 2e-5 rel raw, 3e-5 fused).  The output
-plane is rn_bf16 of the fp32 output bit for bit; on bf16-exact operands the route agrees with the validated bf16x3 route."""
+plane is rn_bf16 of the fp32 output bit for bit; on bf16-exact operands the route agrees with the validated bf16x3 route.  The tile and
+K-stage edges of every configuration, behind redzones and with stated refusals, are in tests/test_gpu_conv_bf16_edges.py."""
 import os
 import sys
 
