@@ -572,6 +572,59 @@ typedef struct straps_wgrad_plan_t {
 } straps_wgrad_plan_t;
 int straps_conv_wgrad_plan(int route, int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad,
                            straps_wgrad_plan_t* out);
+/* The plan of a forward / data-gradient convolution call: which kernel the library launches for a geometry, a tile_cfg and an operand
+ * set, with which tiles, partial blocks, grid and LDS (host arithmetic only; added without a version change).  The compute entry points
+ * launch from this plan, and the block-count queries are fields of it for a fixed operand set:
+ *   straps_conv_stat_blocks          FP32 route, forward: `blocks` (the fp32 rule reads no operand)
+ *   straps_conv_x3_stat_blocks       PLANES, forward, ops = Y | STATS (a training forward): `blocks`
+ *   straps_conv_dgrad_x3_bn_blocks   PLANES, data gradient, ops = Y | RES | BNR_RAW: `blocks` (the plane rules' TILE reads no operand either)
+ *   straps_conv_x3f_stat_blocks      F32_1X1, forward, ops = Y | STATS: `blocks`
+ *   straps_conv_dgrad_x3f_bn_blocks  F32_1X1, data gradient, ops = Y | BNR_RAW: `blocks`.  On this route the tile DOES depend on the operand
+ *                                    set (the lean epilogues decide whether the streaming kernel applies): a caller whose launch has another
+ *                                    epilogue form than these two sizes its partials with straps_conv_plan.
+ *   straps_conv_bf16_tile_choice     BF16, forward, tile_cfg 0: `tile`
+ * route / kind: what straps_conv_fwd | _dgrad, ..._x3 (and _x3p, _x3_bits, _x3_bn, _x3_bn_bits), ..._x3f, straps_conv_fwd_bf16 run.
+ * ops: the operands of the launch, STRAPS_CONV_OP_* or-ed.  Returns STRAPS_EINVAL (text in straps_last_error) for a geometry or a
+ * configuration the route refuses.                                                                                              */
+#define STRAPS_CONV_ROUTE_F32 0
+#define STRAPS_CONV_ROUTE_PLANES 1
+#define STRAPS_CONV_ROUTE_F32_1X1 2
+#define STRAPS_CONV_ROUTE_BF16 3
+#define STRAPS_CONV_KIND_FWD 0
+#define STRAPS_CONV_KIND_DGRAD 1
+#define STRAPS_CONV_FAMILY_IGEMM_F32 0   /* conv_igemm_kernel<bm, bn> */
+#define STRAPS_CONV_FAMILY_PLANE_IM2COL 1 /* conv_igemm_x3_kernel, tile 1..12 of csrc/conv_plan.h */
+#define STRAPS_CONV_FAMILY_PLANE_HALO 2  /* conv_igemm_x3h_kernel, tile = form 1..3 */
+#define STRAPS_CONV_FAMILY_F32OP_TILE 3  /* conv_igemm_x3f_kernel, tile 1 | 2 */
+#define STRAPS_CONV_FAMILY_F32OP_STREAM 4 /* conv1x1_stream_kernel, tile 5, bn = 256 | 128 | 64 */
+#define STRAPS_CONV_FAMILY_BF16_IM2COL 5 /* conv_igemm_x3_kernel with PL chunks per stage, tile 1..8 */
+#define STRAPS_CONV_FAMILY_BF16_HALO 6   /* conv_igemm_x3h_kernel with PL chunks per stage, tile 9 | 10 */
+#define STRAPS_CONV_OP_Y 1         /* fp32 result / dx */
+#define STRAPS_CONV_OP_STATS 2     /* statistics partials */
+#define STRAPS_CONV_OP_SCALE 4     /* folded BatchNorm scale / shift */
+#define STRAPS_CONV_OP_RELU 8
+#define STRAPS_CONV_OP_RES 16      /* residual / addend */
+#define STRAPS_CONV_OP_RES_BITS 32 /* ReLU bits masking the addend */
+#define STRAPS_CONV_OP_BNR_RAW 64  /* fused BatchNorm-backward sums */
+#define STRAPS_CONV_OP_BNR_OUT 128 /* ... with their mask as an fp32 tensor */
+#define STRAPS_CONV_OP_YPLANES 256 /* the result as bf16 plane(s) */
+#define STRAPS_CONV_OP_A_SCALE 512 /* BatchNorm in the operand path (F32_1X1) */
+typedef struct straps_conv_plan_t {
+    int32_t family;
+    int32_t tile;         /* the route's tile number after its rule (tile_cfg & 15 numbering; halo families: the form) */
+    int32_t bm, bn;       /* rows (output pixels) x output channels of a workgroup's tile */
+    int32_t epilogue;     /* 0 shared, 1 lean forward, 2 lean data gradient, 3 bf16 plane */
+    int32_t abn;          /* BatchNorm in the operand path */
+    int32_t ncls;         /* sub-problems of the launch: 1, or the output-parity classes of a stride-2 data gradient */
+    int32_t mt[4];        /* M tiles per class */
+    int32_t nt;           /* N tiles */
+    int32_t part_base[4]; /* first partial block (statistics / BatchNorm-backward sums) of each class */
+    int32_t blocks;       /* partial blocks = sum of mt */
+    int32_t grid_x, grid_y, threads;
+    int32_t lds_bytes;    /* dynamic LDS of the launch */
+} straps_conv_plan_t;
+int straps_conv_plan(int route, int kind, int ops, int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad,
+                     int tile_cfg, straps_conv_plan_t* out);
 /* stem weight gradient straight from the NCHW input (its data gradient: straps_stem_dgrad below). */
 size_t straps_stem_wgrad_workspace_bytes(int batch, int cin, int h, int w);
 int straps_stem_wgrad(const float* x_nchw, const float* dy_nhwc, float* dw_oihw, void* workspace,

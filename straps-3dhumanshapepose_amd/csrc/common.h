@@ -165,16 +165,7 @@ __device__ __forceinline__ void store_planes4_cm(u16* __restrict__ planes, long 
     store_planes4(planes, ps, cm_index(r, c, rows), v);
 }
 
-// Measurement switches (ablation instantiations that compute WRONG results, environment-selected A/B variants) exist only in the tools
-// build: `python tools/build_tools_lib.py` compiles the same sources with -DSTRAPS_TOOLS into tools/bin/libstraps_hip_tools.so.  The
-// product library never reads the environment: STRAPS_TOOL_ENV_INT is its compile-time default there.
-#ifdef STRAPS_TOOLS
-#include <stdlib.h>
-#define STRAPS_TOOL_ENV_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#else
-#define STRAPS_TOOL_ENV_INT(name, dflt) (dflt)
-#endif
-// (the same macro serves switches a sweep changes from call to call: use it in a non-static expression)
+#include "tool_env.h"      // STRAPS_TOOL_ENV_INT: the tools build's A/B switches
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 

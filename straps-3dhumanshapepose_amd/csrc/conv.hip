@@ -275,65 +275,21 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvP p) {
     clk_end(p, clks);
 }
 
-// tile choice from the per-layer sweeps (tools/sweep_conv.py, tools/sweep_igemm_staging.py, B=64): the larger the tile the fewer
-// operand bytes per flop go through L2 -> LDS, but a size only pays while it still yields >= 2 workgroups per CU and the
-// reduction is long enough (K >= 512 / 1024) to amortise its heavier prologue / epilogue: 128x128 first (layer2: 124 vs 111 TFLOP/s),
-// then 128x64 (layer3: 122 vs 113; layer1's 64-channel 3x3 layers: 98 vs 90), otherwise 64x64 whose 5 resident workgroups per CU hide
-// each other's barrier / refill bubbles (layer4's 4096 pixels, the 1x1 down-sampling layers' short K).
-inline void pick_tile(int cfg, long long M, int cout, int kdim, int& bm, int& bn) {
-    cfg &= 15;               // bit 4 selects the register-staged operand path (A/B tools only), bit 5 the traced build
-    const long long mt128 = (M + 127) / 128;
-    if (cfg == 1) { bm = 128; bn = 128; }
-    else if (cfg == 2) { bm = 128; bn = 64; }
-    else if (cfg == 3) { bm = 64; bn = 64; }
-    else if (cfg == 4) { bm = 256; bn = 64; }
-    else if (cout % 128 == 0 && kdim >= 512 && mt128 * (cout / 128) >= 512) { bm = 128; bn = 128; }   // (>= 256 would give layer3 128x128 tiles: +3.5 % in isolation, -0.3 % inside the step)
-    else if (kdim >= 1024 && mt128 * (cout / 64) >= 512) { bm = 128; bn = 64; }
-    else if (cout == 64 && kdim >= 512 && mt128 >= 1024) { bm = 128; bn = 64; }   // layer1: only 64 output channels but 262 144 rows (round 2: 98 vs 90 TFLOP/s forward, 98 vs 94 data gradient, step -0.6 %)
-    else { bm = 64; bn = 64; }
-    if (cout % bn != 0) bn = 64;
-}
-
 template <int BM, int BN, int NS, bool TRACE = false>
-int launch(const ConvP& p0, hipStream_t st) {
-    ConvP p = p0;
-    p.NT = p.Cout / BN;
-    int maxblk = 0;
-    for (int i = 0; i < p.ncls; ++i) {
-        p.cls[i].MT = (p.cls[i].M + BM - 1) / BM;
-        if (p.cls[i].MT * p.NT > maxblk) maxblk = p.cls[i].MT * p.NT;
-    }
-    const size_t lds = NS ? (size_t)NS * (BM + BN) * 32 * sizeof(float) : (size_t)2 * (BM + BN) * LS * sizeof(float);
-    STRAPS_RAISE_LDS((conv_igemm_kernel<BM, BN, NS, TRACE>), lds, "conv_igemm_kernel");
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, NS, TRACE>), dim3(maxblk, p.ncls), dim3(256), lds, st, p);
-    STRAPS_CHECK_LAUNCH("conv_igemm_kernel");
-    return STRAPS_OK;
+int launch(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    return conv_launch<conv_igemm_kernel<BM, BN, NS, TRACE>, BM, BN, 256>(p, pl, "conv_igemm_kernel", st);
 }
 
-// all classes of one launch share the tile choice (made for their total size)
 int dispatch(const ConvP& p, int tile_cfg, hipStream_t st) {
-    int bm, bn, kdim = 0;
-    long long M = 0;
-    for (int i = 0; i < p.ncls; ++i) {
-        M += p.cls[i].M;
-        if (p.cls[i].ntaps * p.Cin > kdim) kdim = p.cls[i].ntaps * p.Cin;
-    }
-    pick_tile(tile_cfg, M, p.Cout, kdim, bm, bn);
-    if (tile_cfg & 32) {        // diagnostic build of the LDS-DMA kernel with the shader-clock trace
-        if (bm == 256) return launch<256, 64, 2, true>(p, st);
-        if (bm == 128 && bn == 128) return launch<128, 128, 2, true>(p, st);
-        if (bm == 128 && bn == 64) return launch<128, 64, 2, true>(p, st);
-        return launch<64, 64, 2, true>(p, st);
-    }
-    if (tile_cfg & 16) {
-        if (bm == 128 && bn == 128) return launch<128, 128, 0>(p, st);
-        if (bm == 128 && bn == 64) return launch<128, 64, 0>(p, st);
-        return launch<64, 64, 0>(p, st);
-    }
-    if (bm == 256) return launch<256, 64, 2>(p, st);
-    if (bm == 128 && bn == 128) return launch<128, 128, 2>(p, st);
-    if (bm == 128 && bn == 64) return launch<128, 64, 2>(p, st);
-    return launch<64, 64, 2>(p, st);
+    ConvPlan pl;
+    const int rc = conv_plan_f32(conv_shape(p), tile_cfg, pl);
+    if (rc != STRAPS_OK) return rc;
+    const int tile = pl.q.tile;
+    if (pl.trace)      // diagnostic build of the LDS-DMA kernel with the shader-clock trace
+        return tile == 4 ? launch<256, 64, 2, true>(p, pl, st) : tile == 1 ? launch<128, 128, 2, true>(p, pl, st) : tile == 2 ? launch<128, 64, 2, true>(p, pl, st)
+                                                                                                                   : launch<64, 64, 2, true>(p, pl, st);
+    if (pl.ns == 0) return tile == 1 ? launch<128, 128, 0>(p, pl, st) : tile == 2 ? launch<128, 64, 0>(p, pl, st) : launch<64, 64, 0>(p, pl, st);
+    return tile == 4 ? launch<256, 64, 2>(p, pl, st) : tile == 1 ? launch<128, 128, 2>(p, pl, st) : tile == 2 ? launch<128, 64, 2>(p, pl, st) : launch<64, 64, 2>(p, pl, st);
 }
 
 }  // namespace
@@ -344,20 +300,32 @@ extern "C" int straps_conv_trace_buffer(long long* trace) {
     return STRAPS_OK;
 }
 
+// statistics partials of straps_conv_fwd: the fp32 rule reads M, cout and the reduction extent only
 extern "C" int straps_conv_stat_blocks(int batch, int ho, int wo, int cout, int kdim, int tile_cfg) {
-    int bm, bn;
-    const long long M = (long long)batch * ho * wo;
-    pick_tile(tile_cfg, M, cout, kdim, bm, bn);
-    return (int)((M + bm - 1) / bm);
+    ConvShape s = {};
+    s.ncls = 1; s.M[0] = (int)((long long)batch * ho * wo); s.ntaps[0] = 1; s.cin = kdim; s.cout = cout;
+    ConvPlan pl;
+    return conv_plan_f32(s, tile_cfg, pl) == STRAPS_OK ? pl.q.blocks : -1;
+}
+
+extern "C" int straps_conv_plan(int route, int kind, int ops, int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int tile_cfg,
+                                straps_conv_plan_t* out) {
+    STRAPS_REQUIRE(out, "straps_conv_plan: null pointer");
+    STRAPS_REQUIRE(route >= STRAPS_CONV_ROUTE_F32 && route <= STRAPS_CONV_ROUTE_BF16, "straps_conv_plan: unknown route %d", route);
+    int rc = conv_geometry_check("straps_conv_plan", route, kind, batch, h, w, cin, cout, kh, kw, stride, pad);
+    if (rc != STRAPS_OK) return rc;
+    ConvPlan pl;
+    rc = conv_plan_for("straps_conv_plan", route, kind, (unsigned)ops, batch, h, w, cin, cout, kh, kw, stride, pad, tile_cfg, pl);
+    if (rc == STRAPS_OK) *out = pl.q;
+    return rc;
 }
 
 extern "C" int straps_conv_fwd(const float* x, const float* w, const float* scale, const float* shift, const float* residual, int relu,
                                float* y, float* stats_partial, int batch, int h, int wdt, int cin, int cout, int kh, int kw, int stride,
                                int pad, int tile_cfg, void* stream) {
     STRAPS_REQUIRE(x && w && y, "straps_conv_fwd: null pointer");
-    STRAPS_REQUIRE(batch > 0 && h > 0 && wdt > 0, "straps_conv_fwd: empty input %dx%dx%d", batch, h, wdt);
-    STRAPS_REQUIRE(cin % 32 == 0 && cout % 64 == 0, "straps_conv_fwd: need cin%%32==0 and cout%%64==0 (cin=%d cout=%d)", cin, cout);
-    STRAPS_REQUIRE(kh >= 1 && kw >= 1 && kh * kw <= 9 && stride >= 1 && pad >= 0, "straps_conv_fwd: bad filter geometry");
+    const int ok = conv_geometry_check("straps_conv_fwd", STRAPS_CONV_ROUTE_F32, STRAPS_CONV_KIND_FWD, batch, h, wdt, cin, cout, kh, kw, stride, pad);
+    if (ok != STRAPS_OK) return ok;
     STRAPS_REQUIRE((scale == nullptr) == (shift == nullptr), "straps_conv_fwd: scale and shift must be given together");
     ConvP p;
     p.x = x; p.w = w;
@@ -374,9 +342,8 @@ extern "C" int straps_conv_fwd(const float* x, const float* w, const float* scal
 extern "C" int straps_conv_dgrad(const float* dy, const float* w_crsk, const float* addend, float* dx, int batch, int h, int wdt,
                                  int cin, int cout, int kh, int kw, int stride, int pad, int tile_cfg, void* stream) {
     STRAPS_REQUIRE(dy && w_crsk && dx, "straps_conv_dgrad: null pointer");
-    STRAPS_REQUIRE(cout % 32 == 0 && cin % 64 == 0, "straps_conv_dgrad: need cout%%32==0 and cin%%64==0 (cin=%d cout=%d)", cin, cout);
-    STRAPS_REQUIRE(stride == 1 || stride == 2, "straps_conv_dgrad: stride must be 1 or 2");
-    STRAPS_REQUIRE(kh * kw <= 9 && kh - 1 - pad >= 0 && kw - 1 - pad >= 0, "straps_conv_dgrad: unsupported filter geometry");
+    const int ok = conv_geometry_check("straps_conv_dgrad", STRAPS_CONV_ROUTE_F32, STRAPS_CONV_KIND_DGRAD, batch, h, wdt, cin, cout, kh, kw, stride, pad);
+    if (ok != STRAPS_OK) return ok;
     hipStream_t st = (hipStream_t)stream;
     ConvP p;
     p.x = dy; p.w = w_crsk;

@@ -17,60 +17,11 @@
 
 namespace {
 
-// tile_cfg & 15 (tools; 0 = the automatic rule below).  All PL = 2 unless noted.
-//   1 = 128x128 (4 waves, 3 stages)      2 = 128x64 (4 waves, 3 stages)      3 = 64x64 (4 waves, 3 stages)
-//   4 = 256x128 (8 waves, 2 stages)      5 = 256x128 (8 waves, 2 stages, software-pipelined loop)
-//   6 = 128x128 (4 waves, 2 stages, PL = 4: cin % 128 == 0)                7 = 128x128 (4 waves, 3 stages, software-pipelined loop)
-//   8 = 128x64 (4 waves, 3 stages, PL = 1: one chunk per stage -- the bf16x3 loop with the planes deleted; A/B reference)
-//   9 = halo patch 128x128 (3 stages, two patch buffers)                  10 = halo patch 128x64 (2 stages, one patch buffer)
-constexpr int kBf16Cfgs = 10;
-
-int cfg_bm(int cfg) { return (cfg == 4 || cfg == 5) ? 256 : cfg == 3 ? 64 : 128; }
-int cfg_bn(int cfg) { return (cfg == 2 || cfg == 3 || cfg == 8 || cfg == 10) ? 64 : 128; }
-
-// the automatic rule, from the MI355X sweep over the 33 resnet18 / resnet50 eval shapes at B = 1, 64, 256 (tools/sweep_conv_bf16.py,
-// profiles/sweep_conv_bf16.json; t128 = 128x128-tile equivalents of the launch).  Summed over the shapes it is within 0.0 / 1.5 / 1.0 % of the
-// per-shape best at B = 1 / 64 / 256 (the bf16x3 route: 1.57 / 2.22 / 2.44x the time):
-//   * 64 output channels, or fewer than 256 tiles: 64x64 -- the grid must fill 256 CUs.  The halo-patch tiles lose here (layer1's 3x3 at
-//     B = 64: 60 against 58 us) and everywhere else: with one plane the im2col ring's nine-fold reuse of the L2 is cheap enough.
-//   * 256 ... 511 tiles: 128x128 / four waves (resnet50's 256-channel layers at B = 64: 27-42 us; the 256x128 tile leaves CUs idle, 34-53 us).
-//   * from 512 tiles on: 256x128 / eight waves, software-pipelined (2-12 % ahead of the plain loop of the same tile on most shapes).
-int pick_tile_bf16(const ConvP& p) {
-    const long long M = p.cls[0].M;
-    const long long t128 = ((M + 127) / 128) * (p.Cout / 128);
-    if (p.Cout % 128 != 0 || t128 < 256) return 3;
-    return t128 < 512 ? 1 : 5;
-}
-
-// which configurations a problem admits (forced ones are checked, never silently replaced)
-const char* cfg_refusal(const ConvP& p, int cfg) {
-    if (cfg < 1 || cfg > kBf16Cfgs) return "unknown tile configuration";
-    if (p.Cout % cfg_bn(cfg) != 0) return "cout is not a multiple of the tile's N extent";
-    if (cfg == 6 && p.Cin % 128 != 0) return "the four-chunk stage needs cin % 128 == 0";
-    if (cfg == 9 && !(halo_patch_slots(p) > 0 && halo_patch_slots(p) <= 208)) return "the halo-patch tile needs a 3x3 / stride-1 layer whose patch fits 208 slots";
-    if (cfg == 10 && !(halo_patch_slots(p) > 0 && halo_patch_slots(p) <= 272)) return "the halo-patch tile needs a 3x3 / stride-1 layer whose patch fits 272 slots";
-    return nullptr;
-}
-
-int dispatch_bf16(ConvP p, int cfg, hipStream_t st) {
+int dispatch_bf16(ConvP p, const ConvPlan& pl, hipStream_t st) {
     // slot s of a stage = K chunk q * PL + s: the "plane strides" are the strides of one 32-channel chunk
     p.xps = (long long)p.xrows * 32;
     p.wps = (long long)p.Cout * 32;
-    switch (cfg) {
-        case 1: return launch_x3<128, 128, 2, 2, 3, 0, false, 3, 2>(p, st);
-        case 2: return launch_x3<128, 64, 2, 2, 3, 0, false, 3, 2>(p, st);
-        case 3: return launch_x3<64, 64, 2, 2, 3, 0, false, 3, 2>(p, st);
-        case 4: return launch_x3<256, 128, 4, 2, 2, 0, false, 3, 2>(p, st);
-        case 5: return launch_x3<256, 128, 4, 2, 2, 0, true, 3, 2>(p, st);
-        case 6: return launch_x3<128, 128, 2, 2, 2, 0, false, 3, 4>(p, st);
-        case 7: return launch_x3<128, 128, 2, 2, 3, 0, true, 3, 2>(p, st);
-        case 8: return launch_x3<128, 64, 2, 2, 3, 0, false, 3, 1>(p, st);
-        case 9: return launch_x3h<128, 128, 2, 2, 3, 208, 2, 3, 2>(p, st);
-        case 10: return launch_x3h<128, 64, 2, 2, 2, 272, 1, 3, 2>(p, st);
-        default: break;
-    }
-    straps_set_error("straps_conv_fwd_bf16: tile configuration %d does not exist", cfg);
-    return STRAPS_EUNSUPPORTED;
+    return launch_x3_tiles<kBf16Tile, 3, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(p, pl, st);
 }
 
 // x [rows][C] fp32 -> rn_bf16(x) as one chunk-major plane; four channels per thread (one 8-byte store)
@@ -132,14 +83,12 @@ extern "C" int straps_pack_conv_weight_bf16(const float* w_oihw, unsigned short*
     return STRAPS_OK;
 }
 
-// the tile configuration straps_conv_fwd_bf16 takes for tile_cfg = 0 (1..10, see above); -1 for a geometry it does not cover
+// the tile configuration straps_conv_fwd_bf16 takes for tile_cfg = 0 (1..10, conv_plan.h); -1 for a geometry it does not cover
 extern "C" int straps_conv_bf16_tile_choice(int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad) {
     if (batch <= 0 || h <= 0 || w <= 0 || cin % 64 != 0 || cout % 64 != 0 || kh < 1 || kw < 1 || kh * kw > 9 || stride < 1 || pad < 0) return -1;
-    ConvP p;
-    p.x = nullptr; p.w = nullptr; p.xps = p.wps = 0;
-    if (conv_fwd_problem(p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, batch, h, w, cin, cout, kh, kw, stride, pad) != STRAPS_OK) return -1;
-    if (p.cls[0].M <= 0) return -1;
-    return pick_tile_bf16(p);
+    ConvPlan pl;
+    return conv_plan_for("straps_conv_bf16_tile_choice", STRAPS_CONV_ROUTE_BF16, STRAPS_CONV_KIND_FWD, STRAPS_CONV_OP_Y | STRAPS_CONV_OP_YPLANES, batch, h, w, cin, cout,
+                         kh, kw, stride, pad, 0, pl) == STRAPS_OK ? pl.q.tile : -1;
 }
 
 extern "C" int straps_conv_fwd_bf16(const unsigned short* x1, const unsigned short* w1_krsc, const float* scale, const float* shift, const float* residual,
@@ -147,23 +96,19 @@ extern "C" int straps_conv_fwd_bf16(const unsigned short* x1, const unsigned sho
                                     int pad, int tile_cfg, void* stream) {
     STRAPS_REQUIRE(x1 && w1_krsc, "straps_conv_fwd_bf16: null pointer");
     STRAPS_REQUIRE(y || y_plane, "straps_conv_fwd_bf16: no output (y and y_plane are both NULL)");
-    STRAPS_REQUIRE(batch > 0 && h > 0 && wdt > 0, "straps_conv_fwd_bf16: empty input %dx%dx%d", batch, h, wdt);
-    STRAPS_REQUIRE(cin % 64 == 0 && cout % 64 == 0, "straps_conv_fwd_bf16: need cin%%64==0 and cout%%64==0 (cin=%d cout=%d)", cin, cout);
-    STRAPS_REQUIRE(kh >= 1 && kw >= 1 && kh * kw <= 9 && stride >= 1 && pad >= 0, "straps_conv_fwd_bf16: bad filter geometry");
+    const int ok = conv_geometry_check("straps_conv_fwd_bf16", STRAPS_CONV_ROUTE_BF16, STRAPS_CONV_KIND_FWD, batch, h, wdt, cin, cout, kh, kw, stride, pad);
+    if (ok != STRAPS_OK) return ok;
     STRAPS_REQUIRE((scale == nullptr) == (shift == nullptr), "straps_conv_fwd_bf16: scale and shift must be given together");
     STRAPS_REQUIRE((reinterpret_cast<uintptr_t>(x1) & 15) == 0 && (reinterpret_cast<uintptr_t>(w1_krsc) & 15) == 0,
                    "straps_conv_fwd_bf16: x1 and w1_krsc must be 16-byte aligned");
-    STRAPS_REQUIRE(tile_cfg >= 0 && tile_cfg <= kBf16Cfgs, "straps_conv_fwd_bf16: tile_cfg must be in [0, %d] (got %d)", kBf16Cfgs, tile_cfg);
     ConvP p;
     p.x = reinterpret_cast<const float*>(x1); p.w = reinterpret_cast<const float*>(w1_krsc);
     p.xps = p.wps = 0;
     const int rc = conv_fwd_problem(p, scale, shift, residual, relu, y, nullptr, batch, h, wdt, cin, cout, kh, kw, stride, pad);
     if (rc != STRAPS_OK) return rc;
-    STRAPS_REQUIRE(p.cls[0].M > 0, "straps_conv_fwd_bf16: empty output");
-    const int cfg = tile_cfg ? tile_cfg : pick_tile_bf16(p);
-    const char* why = cfg_refusal(p, cfg);
-    STRAPS_REQUIRE(!why, "straps_conv_fwd_bf16: tile_cfg %d: %s", cfg, why);
     p.yplanes = y_plane;
     p.yps = 0;
-    return dispatch_bf16(p, cfg, (hipStream_t)stream);
+    ConvPlan pl;
+    const int rp = conv_plan_bf16("straps_conv_fwd_bf16", conv_shape(p), tile_cfg, pl);      // (a forced configuration is checked, never silently replaced)
+    return rp != STRAPS_OK ? rp : dispatch_bf16(p, pl, (hipStream_t)stream);
 }

@@ -3,6 +3,7 @@
 // Included by conv.hip (exact-fp32 MFMA) and conv_x3.hip (three-plane bf16 operands, six products per term).
 #pragma once
 #include "common.h"
+#include "conv_plan.h"
 #include <type_traits>
 #include <utility>
 
@@ -783,21 +784,6 @@ struct LeanDgradEpilogue {
     }
 };
 
-// which epilogue a problem takes: 1 = the lean forward form (raw result + statistics: a training step's forward; one class, no remap), 2 = the lean
-// data-gradient form (addend with optional ReLU bits, BatchNorm sums with bits or the re-derived mask; any class structure), 0 = the shared epilogue
-inline int lean_epilogue_choice(const ConvP& p) {
-    if (p.yplanes || p.bnr_out || !p.y || p.scale || p.relu) return 0;
-    const ConvP::Class& c = p.cls[0];
-    const bool remap = p.omul != 1 || c.oah != 0 || c.oaw != 0 || p.OH != c.Mh || p.OW != c.Mw;
-    if (!p.res && !p.bnr_raw && !p.res_bits) return (p.ncls == 1 && !remap) ? 1 : 0;
-    if (!p.stats && (p.res || p.bnr_raw) && (!p.res_bits || p.res)) {
-        for (int i = 0; i < p.ncls; ++i)
-            if (p.cls[i].ntaps == 0) return 0;      // (the dead parity classes of a 1x1 / stride-2 gradient: dx = addend there -- the shared epilogue's row form)
-        return 2;
-    }
-    return 0;
-}
-
 // the epilogue object of the plane kernels (conv_x3_kernels.h): the look-ahead epilogue for EPI = 0, nothing for the lean forms
 template <int BM, int BN, int WGM, int WGN, int EPI>
 struct X3Epilogue {
@@ -974,6 +960,68 @@ inline int conv_dgrad_problem(ConvP& p, const float* addend, float* dx, int batc
             p.cls[b] = p.cls[b - 1];
             p.cls[b - 1] = t;
         }
+    return STRAPS_OK;
+}
+
+// ---- the launch plan (conv_plan.h): its two inputs read off a ConvP, and the plan written back into the launch's copy ----------------------
+
+// does the halo-patch kernel (BM = 128) cover this problem?  3x3 / stride 1 / pad 1 as ONE class over the full map, tiles of whole rows
+// inside one image or of whole images, no ragged tile -> the patch's slots (the caller holds them to the kernel's capacity), else 0
+inline int halo_patch_slots(const ConvP& p) {
+    constexpr int BM = 128;
+    if (p.ncls != 1 || p.stride != 1 || p.omul != 1) return 0;
+    const ConvP::Class& c = p.cls[0];
+    if (c.ntaps != 9 || c.Mh != p.H || c.Mw != p.W || p.OH != p.H || p.OW != p.W || c.oah != 0 || c.oaw != 0 || c.M % BM != 0) return 0;
+    for (int t = 0; t < 9; ++t)
+        if (c.tap_dh[t] < -1 || c.tap_dh[t] > 1 || c.tap_dw[t] < -1 || c.tap_dw[t] > 1) return 0;
+    const int HW = p.H * p.W;
+    if (BM >= HW) { if (BM % HW != 0) return 0; return (BM / HW) * (p.H + 2) * (p.W + 2); }
+    if (BM % p.W != 0 || HW % BM != 0) return 0;
+    return (BM / p.W + 2) * (p.W + 2);
+}
+
+inline ConvShape conv_shape(const ConvP& p) {
+    ConvShape s = {};
+    s.ncls = p.ncls; s.cin = p.Cin; s.cout = p.Cout;
+    for (int i = 0; i < p.ncls; ++i) { s.M[i] = p.cls[i].M; s.ntaps[i] = p.cls[i].ntaps; }
+    const ConvP::Class& c = p.cls[0];
+    s.remap = p.omul != 1 || c.oah != 0 || c.oaw != 0 || p.OH != c.Mh || p.OW != c.Mw;
+    s.halo_slots = halo_patch_slots(p);
+    return s;
+}
+
+// the operand mask of a launch
+inline unsigned conv_ops(const ConvP& p) {
+    return (p.y ? STRAPS_CONV_OP_Y : 0) | (p.stats ? STRAPS_CONV_OP_STATS : 0) | (p.scale ? STRAPS_CONV_OP_SCALE : 0) | (p.relu ? STRAPS_CONV_OP_RELU : 0) |
+           (p.res ? STRAPS_CONV_OP_RES : 0) | (p.res_bits ? STRAPS_CONV_OP_RES_BITS : 0) | (p.bnr_raw ? STRAPS_CONV_OP_BNR_RAW : 0) |
+           (p.bnr_out ? STRAPS_CONV_OP_BNR_OUT : 0) | (p.yplanes ? STRAPS_CONV_OP_YPLANES : 0) | (p.a_scale ? STRAPS_CONV_OP_A_SCALE : 0);
+}
+
+// the plan of a route for a geometry and an operand set, without a launch: the block-count queries and straps_conv_plan
+inline int conv_plan_for(const char* who, int route, int kind, unsigned ops, int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad,
+                         int tile_cfg, ConvPlan& pl) {
+    ConvP p;
+    p.x = p.w = nullptr; p.xps = p.wps = 0;
+    const int rc = kind == STRAPS_CONV_KIND_FWD ? conv_fwd_problem(p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, batch, h, w, cin, cout, kh, kw, stride, pad)
+                                                : conv_dgrad_problem(p, nullptr, nullptr, batch, h, w, cin, cout, kh, kw, stride, pad);
+    return rc != STRAPS_OK ? rc : conv_plan_route(who, route, conv_shape(p), tile_cfg, ops, pl);
+}
+
+// THE launcher of the implicit-GEMM kernels: tiles, partial bases, grid, block and LDS are the plan's.  An instantiation that is not the plan's tile
+// is an error, not a launch.
+template <auto KERNEL, int BM, int BN, int THREADS>
+int conv_launch(const ConvP& p0, const ConvPlan& pl, const char* name, hipStream_t st) {
+    const straps_conv_plan_t& q = pl.q;
+    if (q.bm != BM || q.bn != BN || q.threads != THREADS || q.ncls != p0.ncls) {
+        straps_set_error("%s<%d, %d>, %d threads, %d classes: not the plan's %d x %d tile, %d threads, %d classes", name, BM, BN, THREADS, p0.ncls, q.bm, q.bn, q.threads, q.ncls);
+        return STRAPS_EINVAL;
+    }
+    ConvP p = p0;
+    p.NT = q.nt;
+    for (int i = 0; i < p.ncls; ++i) { p.cls[i].MT = q.mt[i]; p.bnr_base[i] = q.part_base[i]; }
+    STRAPS_RAISE_LDS(KERNEL, q.lds_bytes, name);
+    hipLaunchKernelGGL(KERNEL, dim3(q.grid_x, q.grid_y), dim3(q.threads), q.lds_bytes, st, p);
+    STRAPS_CHECK_LAUNCH(name);
     return STRAPS_OK;
 }
 

@@ -535,51 +535,22 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_x3h_kernel(ConvP p)
     clk_end(p, clk);
 }
 
-template <int BM, int BN, int WGM, int WGN, int NST, int PS, int PBUF = 2, int EPI = 0, int PL = 0>
-int launch_x3h(const ConvP& p0, hipStream_t st) {
-    ConvP p = p0;
-    p.NT = p.Cout / BN;
-    p.cls[0].MT = p.cls[0].M / BM;
-    p.bnr_base[0] = 0;
-    const size_t lds = ((size_t)PBUF * (PL ? PL : 3) * PS + (size_t)NST * (PL ? PL : 3) * BN) * 32 * sizeof(u16);
-    STRAPS_RAISE_LDS((conv_igemm_x3h_kernel<BM, BN, WGM, WGN, NST, PS, PBUF, EPI, PL>), lds, "conv_igemm_x3h_kernel");
-    hipLaunchKernelGGL((conv_igemm_x3h_kernel<BM, BN, WGM, WGN, NST, PS, PBUF, EPI, PL>), dim3(p.cls[0].MT * p.NT, 1), dim3(64 * WGM * WGN), lds, st, p);
-    STRAPS_CHECK_LAUNCH("conv_igemm_x3h_kernel");
-    return STRAPS_OK;
+// the instantiation of row T of one of conv_plan.h's tile tables (ABL: tools only, and only on the tiles without the pipelined loop) ...
+template <const ConvTile* TILES, int T, int EPI, int ABL>
+int launch_x3_tile(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    constexpr ConvTile t = TILES[T];
+    if constexpr (t.ps != 0)
+        return conv_launch<conv_igemm_x3h_kernel<t.bm, t.bn, t.wgm, t.wgn, t.nst, t.ps, t.pbuf, EPI, t.pl>, t.bm, t.bn, 64 * t.wgm * t.wgn>(p, pl, "conv_igemm_x3h_kernel", st);
+    else
+        return conv_launch<conv_igemm_x3_kernel<t.bm, t.bn, t.wgm, t.wgn, t.nst, t.pipe ? 0 : ABL, t.pipe, EPI, t.pl>, t.bm, t.bn, 64 * t.wgm * t.wgn>(p, pl, "conv_igemm_x3_kernel", st);
 }
-
-// does the halo-patch kernel (BM = 128) cover this problem?  3x3 / stride 1 / pad 1 as ONE class over the full map, tiles of whole rows
-// inside one image or of whole images, no ragged tile, patch within the slot capacity
-inline int halo_patch_slots(const ConvP& p) {
-    constexpr int BM = 128;
-    if (p.ncls != 1 || p.stride != 1 || p.omul != 1) return 0;
-    const ConvP::Class& c = p.cls[0];
-    if (c.ntaps != 9 || c.Mh != p.H || c.Mw != p.W || p.OH != p.H || p.OW != p.W || c.oah != 0 || c.oaw != 0 || c.M % BM != 0) return 0;
-    for (int t = 0; t < 9; ++t)
-        if (c.tap_dh[t] < -1 || c.tap_dh[t] > 1 || c.tap_dw[t] < -1 || c.tap_dw[t] > 1) return 0;
-    const int HW = p.H * p.W;
-    if (BM >= HW) { if (BM % HW != 0) return 0; return (BM / HW) * (p.H + 2) * (p.W + 2); }
-    if (BM % p.W != 0 || HW % BM != 0) return 0;
-    return (BM / p.W + 2) * (p.W + 2);
-}
-
-template <int BM, int BN, int WGM, int WGN, int NST, int ABL = 0, bool PIPE = false, int EPI = 0, int PL = 0>
-int launch_x3(const ConvP& p0, hipStream_t st) {
-    ConvP p = p0;
-    p.NT = p.Cout / BN;
-    int maxblk = 0;
-    int base = 0;
-    for (int i = 0; i < p.ncls; ++i) {
-        p.cls[i].MT = (p.cls[i].M + BM - 1) / BM;
-        if (p.cls[i].MT * p.NT > maxblk) maxblk = p.cls[i].MT * p.NT;
-        p.bnr_base[i] = base;                   // (BatchNorm-backward partials: one block per M tile, classes one after the other)
-        base += p.cls[i].MT;
-    }
-    const size_t lds = (size_t)NST * (PL ? PL : 3) * (BM + BN) * 32 * sizeof(u16);
-    STRAPS_RAISE_LDS((conv_igemm_x3_kernel<BM, BN, WGM, WGN, NST, ABL, PIPE, EPI, PL>), lds, "conv_igemm_x3_kernel");
-    hipLaunchKernelGGL((conv_igemm_x3_kernel<BM, BN, WGM, WGN, NST, ABL, PIPE, EPI, PL>), dim3(maxblk, p.ncls), dim3(64 * WGM * WGN), lds, st, p);
-    STRAPS_CHECK_LAUNCH("conv_igemm_x3_kernel");
-    return STRAPS_OK;
+// ... and a dispatcher's set of them: the rows T... with one epilogue; the plan names the row
+template <const ConvTile* TILES, int EPI, int ABL, int... T>
+int launch_x3_tiles(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    int rc = STRAPS_EUNSUPPORTED;
+    if (!((pl.q.tile == T && ((rc = launch_x3_tile<TILES, T, EPI, ABL>(p, pl, st)), true)) || ...))
+        straps_set_error("conv_igemm_x3 kernels: tile %d of family %d has no instantiation with epilogue %d", pl.q.tile, pl.q.family, EPI);
+    return rc;
 }
 
 }  // namespace

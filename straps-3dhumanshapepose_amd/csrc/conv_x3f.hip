@@ -53,9 +53,9 @@ __device__ __forceinline__ void lds_write_b64(unsigned addr, const u32x2& v) {
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
 }
 
-// tools build: STRAPS_X3F_ABL = 1 no result stores, 2 no A loads (constants instead), 4 no MFMAs, 8 no statistics partials (any sum; wrong results)
-inline void x3f_ablate(ConvP& p) {
-    p.abl = STRAPS_TOOL_ENV_INT("STRAPS_X3F_ABL", 0);
+// tools build (the plan's abl = STRAPS_X3F_ABL): 1 no result stores, 2 no A loads (constants instead), 4 no MFMAs, 8 no statistics partials (any sum; wrong results)
+inline void x3f_ablate(ConvP& p, int abl) {
+    p.abl = abl;
     if (p.abl & 1) p.y = nullptr;
     if (p.abl & 8) p.stats = nullptr;
 }
@@ -506,136 +506,48 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv1x1_stream_kernel(ConvP
     clk_end(p, clk);
 }
 
-// which epilogue a problem takes (conv_igemm.h: lean_epilogue_choice); the tools build can switch the lean forms off for the A/B
-inline int x3f_epilogue(const ConvP& p) {
-    if (STRAPS_TOOL_ENV_INT("STRAPS_X3F_LEAN", 1) == 0) return 0;
-    if (p.cls[0].ntaps != 1) return 0;
-    return lean_epilogue_choice(p);
-}
-
-// LDS of the streaming kernel for a reduction extent of cin channels
-template <int BM, int BN, int WGM, bool BRES>
-size_t stream_lds_bytes(int cin) {
-    return (size_t)2 * 3 * BM * 32 * 2 + (size_t)3 * (BRES ? cin / 32 : 2) * BN * 32 * 2 + (size_t)WGM * BN * 4 * 4 + (size_t)2 * cin * 4;
-}
-
-template <int BM, int BN, int WGM, int WGN, bool ABN, bool BRES, int EPI>
-int launch_stream_abn(const ConvP& p0, hipStream_t st) {
-    ConvP p = p0;
-    p.NT = p.Cout / BN;
-    p.cls[0].MT = (p.cls[0].M + BM - 1) / BM;
-    p.bnr_base[0] = 0;
-    const size_t lds = stream_lds_bytes<BM, BN, WGM, BRES>(p.Cin);
-    STRAPS_REQUIRE(lds <= 160 * 1024, "conv1x1_stream_kernel: the operand images do not fit the LDS (cin=%d, BN=%d)", p.Cin, BN);
-    // as many workgroups as stay resident (LDS decides), at most one per M tile; a multiple of the N tiles (a workgroup keeps ONE weight tile)
-    const int per_cu = (int)((160 * 1024) / lds) > 2 ? 2 : (int)((160 * 1024) / lds);
-    int wgs = 256 * per_cu / p.NT;
-    {
-        const int f = STRAPS_TOOL_ENV_INT("STRAPS_X3F_STREAM_WGS", 0);      // (tools: workgroups per N tile; a large number = one tile per workgroup, nothing persistent)
-        if (f > 0) wgs = f;
-    }
-    if (wgs > p.cls[0].MT) wgs = p.cls[0].MT;
-    if (wgs < 1) wgs = 1;
-    x3f_ablate(p);
-    STRAPS_RAISE_LDS((conv1x1_stream_kernel<BM, BN, WGM, WGN, ABN, BRES, EPI>), lds, "conv1x1_stream_kernel");
-    hipLaunchKernelGGL((conv1x1_stream_kernel<BM, BN, WGM, WGN, ABN, BRES, EPI>), dim3(wgs * p.NT), dim3(64 * WGM * WGN), lds, st, p);
-    STRAPS_CHECK_LAUNCH("conv1x1_stream_kernel");
-    return STRAPS_OK;
-}
+// the instantiation of a tile for the plan's epilogue form and operand-path BatchNorm (the lean data-gradient form has none)
 template <int BM, int BN, int WGM, int WGN, bool BRES>
-int launch_stream(const ConvP& p, hipStream_t st) {
-    if (x3f_epilogue(p) == 2) return launch_stream_abn<BM, BN, WGM, WGN, false, BRES, 2>(p, st);
-    return p.a_scale ? launch_stream_abn<BM, BN, WGM, WGN, true, BRES, 1>(p, st) : launch_stream_abn<BM, BN, WGM, WGN, false, BRES, 1>(p, st);
+int launch_stream(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    constexpr int TH = 64 * WGM * WGN;
+    if (pl.q.epilogue == 2) return conv_launch<conv1x1_stream_kernel<BM, BN, WGM, WGN, false, BRES, 2>, BM, BN, TH>(p, pl, "conv1x1_stream_kernel", st);
+    return pl.q.abn ? conv_launch<conv1x1_stream_kernel<BM, BN, WGM, WGN, true, BRES, 1>, BM, BN, TH>(p, pl, "conv1x1_stream_kernel", st)
+                    : conv_launch<conv1x1_stream_kernel<BM, BN, WGM, WGN, false, BRES, 1>, BM, BN, TH>(p, pl, "conv1x1_stream_kernel", st);
+}
+template <int BM, int EPI>
+int launch_x3f_epi(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    if constexpr (EPI != 2)
+        if (pl.q.abn) return conv_launch<conv_igemm_x3f_kernel<BM, 64, 2, 2, 2, true, EPI>, BM, 64, 256>(p, pl, "conv_igemm_x3f_kernel", st);
+    return conv_launch<conv_igemm_x3f_kernel<BM, 64, 2, 2, 2, false, EPI>, BM, 64, 256>(p, pl, "conv_igemm_x3f_kernel", st);
+}
+template <int BM>
+int launch_x3f(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    return pl.q.epilogue == 1 ? launch_x3f_epi<BM, 1>(p, pl, st) : pl.q.epilogue == 2 ? launch_x3f_epi<BM, 2>(p, pl, st) : launch_x3f_epi<BM, 0>(p, pl, st);
 }
 
-// width of the streaming kernel's output-channel tile for this problem, 0 = not eligible (several classes, a reduction extent that is not a
-// multiple of 64).  256 wide with resident weights where all of K fits beside it (K = 64), else 128 / 64 wide with the weight ring.
-inline int stream_bn(const ConvP& p) {
-    if (p.ncls != 1 || p.cls[0].ntaps != 1 || p.Cin % 64 != 0 || x3f_epilogue(p) == 0) return 0;
-    if (p.Cout % 256 == 0 && p.Cin <= 64) return 256;
-    return p.Cout % 128 == 0 && p.Cin < p.Cout ? 128 : 64;
+int dispatch_x3f(const char* who, ConvP p, int tile_cfg, hipStream_t st) {
+    ConvPlan pl;
+    const int rc = conv_plan_x3f(who, conv_shape(p), tile_cfg, conv_ops(p), pl);
+    if (rc != STRAPS_OK) return rc;
+    x3f_ablate(p, pl.abl);
+    if (pl.q.family == STRAPS_CONV_FAMILY_F32OP_STREAM)
+        return pl.q.bn == 256 ? launch_stream<64, 256, 2, 4, true>(p, pl, st) : pl.q.bn == 128 ? launch_stream<128, 128, 2, 4, false>(p, pl, st)
+                                                                                                : launch_stream<128, 64, 2, 2, false>(p, pl, st);
+    return pl.q.tile == 2 ? launch_x3f<64>(p, pl, st) : launch_x3f<128>(p, pl, st);
 }
 
-template <int BM, int BN, int WGM, int WGN, int NST, bool ABN, int EPI>
-int launch_x3f_abn(const ConvP& p0, hipStream_t st) {
-    ConvP p = p0;
-    p.NT = p.Cout / BN;
-    int maxblk = 0;
-    int base = 0;
-    for (int i = 0; i < p.ncls; ++i) {
-        p.cls[i].MT = (p.cls[i].M + BM - 1) / BM;
-        if (p.cls[i].MT * p.NT > maxblk) maxblk = p.cls[i].MT * p.NT;
-        p.bnr_base[i] = base;                   // (BatchNorm-backward partials: one block per M tile, classes one after the other)
-        base += p.cls[i].MT;
-    }
-    const size_t lds = (size_t)NST * 3 * (BM + BN) * 32 * sizeof(u16);
-    x3f_ablate(p);
-    STRAPS_RAISE_LDS((conv_igemm_x3f_kernel<BM, BN, WGM, WGN, NST, ABN, EPI>), lds, "conv_igemm_x3f_kernel");
-    hipLaunchKernelGGL((conv_igemm_x3f_kernel<BM, BN, WGM, WGN, NST, ABN, EPI>), dim3(maxblk, p.ncls), dim3(64 * WGM * WGN), lds, st, p);
-    STRAPS_CHECK_LAUNCH("conv_igemm_x3f_kernel");
-    return STRAPS_OK;
+// the block-count queries: the plan's partial blocks for the operand set of a training step's launch
+int x3f_query_blocks(const char* who, int kind, unsigned ops, int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int tile_cfg) {
+    ConvPlan pl;
+    if (!(kh == 1 && kw == 1 && pad == 0) || (kind == STRAPS_CONV_KIND_DGRAD && !(stride == 1 || stride == 2))) return -1;
+    return conv_plan_for(who, STRAPS_CONV_ROUTE_F32_1X1, kind, ops, batch, h, w, cin, cout, kh, kw, stride, pad, tile_cfg, pl) == STRAPS_OK ? pl.q.blocks : -1;
 }
-template <int BM, int BN, int WGM, int WGN, int NST>
-int launch_x3f(const ConvP& p, hipStream_t st) {
-    switch (x3f_epilogue(p)) {
-        case 1: return p.a_scale ? launch_x3f_abn<BM, BN, WGM, WGN, NST, true, 1>(p, st) : launch_x3f_abn<BM, BN, WGM, WGN, NST, false, 1>(p, st);
-        case 2: return launch_x3f_abn<BM, BN, WGM, WGN, NST, false, 2>(p, st);
-        default: return p.a_scale ? launch_x3f_abn<BM, BN, WGM, WGN, NST, true, 0>(p, st) : launch_x3f_abn<BM, BN, WGM, WGN, NST, false, 0>(p, st);
-    }
-}
-
-// tile_cfg & 15: 0 = auto, 1 = 128x64 (4 waves, 2 stages: 72 KB of LDS, two workgroups per CU), 2 = 64x64 (4 waves, 2 stages: 48 KB, three per CU),
-// 5 = the streaming kernel (persistent workgroups, 128-row
-// tiles, resident weights) where the problem is eligible (stream_bn), else as 0.
-// The 1x1 layers this kernel exists for are byte-bound: what counts is that a CU always has a workgroup in its load phase beside one in its
-// store phase, i.e. SEVERAL workgroups per CU, not a large tile (rule below from tools/sweep_conv_x3f_cold.py, profiles/r06_x3f_cold_sweep.txt)
-inline int pick_tile_x3f(int cfg, long long M, int cout, int ncls, int& bm, int& bn, int sbn = 0) {
-    cfg &= 15;
-    // the streaming kernel: explicitly (5), or by rule for long problems -- at least four 128-row tiles per workgroup
-    if ((cfg == 5 || (cfg == 0 && M >= 4 * 128 * (256 / (cout / (sbn ? sbn : cout))))) && sbn) { bm = sbn == 256 ? 64 : 128; bn = sbn; return 5; }
-    if (cfg == 5) cfg = 0;
-    if (cfg == 0) {
-        const long long t64 = ((M / ncls + 127) / 128) * (cout / 64);       // 128x64 tiles of a class
-        cfg = t64 < 512 ? 2 : 1;
-    }
-    if (cfg < 1 || cfg > 2) cfg = 1;
-    bm = cfg == 2 ? 64 : 128;
-    bn = 64;
-    return cfg;
-}
-
-int dispatch_x3f(const ConvP& p, int tile_cfg, hipStream_t st) {
-    int bm, bn;
-    long long M = 0;
-    for (int i = 0; i < p.ncls; ++i) M += p.cls[i].M;
-    switch (pick_tile_x3f(tile_cfg, M, p.Cout, p.ncls, bm, bn, stream_bn(p))) {
-        case 5:
-            if (bn == 256) return launch_stream<64, 256, 2, 4, true>(p, st);
-            if (bn == 128) return launch_stream<128, 128, 2, 4, false>(p, st);
-            return launch_stream<128, 64, 2, 2, false>(p, st);
-        case 2: return launch_x3f<64, 64, 2, 2, 2>(p, st);
-        default: return launch_x3f<128, 64, 2, 2, 2>(p, st);
-    }
-}
-
-int x3f_blocks(const ConvP& p, int tile_cfg) {
-    int bm, bn;
-    long long M = 0;
-    for (int i = 0; i < p.ncls; ++i) M += p.cls[i].M;
-    pick_tile_x3f(tile_cfg, M, p.Cout, p.ncls, bm, bn, stream_bn(p));
-    int blocks = 0;
-    for (int i = 0; i < p.ncls; ++i) blocks += (p.cls[i].M + bm - 1) / bm;
-    return blocks;
-}
-
-// single-tap geometry only: a 1x1 filter without padding
-inline bool x3f_geometry_ok(int kh, int kw, int pad) { return kh == 1 && kw == 1 && pad == 0; }
 
 }  // namespace
 
 // does straps_conv_fwd_x3f / straps_conv_dgrad_x3f cover this geometry?  (hosts route the other layers through the plane kernels)
 extern "C" int straps_conv_x3f_supported(int cin, int cout, int kh, int kw, int stride, int pad) {
-    return x3f_geometry_ok(kh, kw, pad) && (stride == 1 || stride == 2) && cin % 64 == 0 && cout % 64 == 0;
+    return kh == 1 && kw == 1 && pad == 0 && (stride == 1 || stride == 2) && cin % 64 == 0 && cout % 64 == 0;
 }
 
 // 1x1 convolution on the bf16 matrix pipe with the A operand read from the fp32 NHWC tensor x [batch][h][w][cin] (see the head of this
@@ -645,9 +557,8 @@ extern "C" int straps_conv_fwd_x3f(const float* x, const float* a_scale, const f
                                    const float* scale, const float* shift, const float* residual, int relu, float* y, float* stats_partial,
                                    int batch, int h, int wdt, int cin, int cout, int kh, int kw, int stride, int pad, int tile_cfg, void* stream) {
     STRAPS_REQUIRE(x && w3 && y, "straps_conv_fwd_x3f: null pointer");
-    STRAPS_REQUIRE(batch > 0 && h > 0 && wdt > 0, "straps_conv_fwd_x3f: empty input %dx%dx%d", batch, h, wdt);
-    STRAPS_REQUIRE(x3f_geometry_ok(kh, kw, pad) && stride >= 1, "straps_conv_fwd_x3f: 1x1 filters without padding only (kh=%d kw=%d pad=%d)", kh, kw, pad);
-    STRAPS_REQUIRE(cin % 32 == 0 && cout % 64 == 0, "straps_conv_fwd_x3f: need cin%%32==0 and cout%%64==0 (cin=%d cout=%d)", cin, cout);
+    const int ok = conv_geometry_check("straps_conv_fwd_x3f", STRAPS_CONV_ROUTE_F32_1X1, STRAPS_CONV_KIND_FWD, batch, h, wdt, cin, cout, kh, kw, stride, pad);
+    if (ok != STRAPS_OK) return ok;
     STRAPS_REQUIRE((scale == nullptr) == (shift == nullptr), "straps_conv_fwd_x3f: scale and shift must be given together");
     STRAPS_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "straps_conv_fwd_x3f: a_scale and a_shift must be given together");
     STRAPS_REQUIRE(w_plane_stride % 8 == 0, "straps_conv_fwd_x3f: the plane stride must be a multiple of 8 elements");
@@ -659,16 +570,12 @@ extern "C" int straps_conv_fwd_x3f(const float* x, const float* a_scale, const f
     const int rc = conv_fwd_problem(p, scale, shift, residual, relu, y, stats_partial, batch, h, wdt, cin, cout, kh, kw, stride, pad);
     if (rc != STRAPS_OK) return rc;
     p.a_scale = a_scale; p.a_shift = a_shift; p.a_relu = a_relu;
-    return dispatch_x3f(p, tile_cfg, (hipStream_t)stream);
+    return dispatch_x3f("straps_conv_fwd_x3f", p, tile_cfg, (hipStream_t)stream);
 }
 
-// number of [cout][2] statistics partials straps_conv_fwd_x3f writes for this geometry (= its M tiles)
+// number of [cout][2] statistics partials straps_conv_fwd_x3f writes for this geometry (= its M tiles) in a training forward (raw result + statistics)
 extern "C" int straps_conv_x3f_stat_blocks(int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int tile_cfg) {
-    ConvP p;
-    p.x = nullptr; p.w = nullptr; p.xps = p.wps = 0;
-    if (!x3f_geometry_ok(kh, kw, pad) || conv_fwd_problem(p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, batch, h, w, cin, cout, kh, kw, stride, pad) != STRAPS_OK) return -1;
-    p.y = reinterpret_cast<float*>(16);      // (stand-in, as above: a training forward)
-    return x3f_blocks(p, tile_cfg);
+    return x3f_query_blocks("straps_conv_x3f_stat_blocks", STRAPS_CONV_KIND_FWD, STRAPS_CONV_OP_Y | STRAPS_CONV_OP_STATS, batch, h, w, cin, cout, kh, kw, stride, pad, tile_cfg);
 }
 
 // data gradient of a 1x1 convolution with the gradient dy read as the fp32 tensor [batch][ho][wo][cout] (no planes of it need exist): every
@@ -680,8 +587,8 @@ extern "C" int straps_conv_dgrad_x3f(const float* dy, const unsigned short* w3_c
                                      const float* bn_raw, const unsigned* bn_out_bits, const float* bn_mask_scale, const float* bn_mask_shift,
                                      const float* bn_mean, const float* bn_invstd, double* bn_partials, void* stream) {
     STRAPS_REQUIRE(dy && w3_crsk && dx, "straps_conv_dgrad_x3f: null pointer");
-    STRAPS_REQUIRE(x3f_geometry_ok(kh, kw, pad) && (stride == 1 || stride == 2), "straps_conv_dgrad_x3f: 1x1 filters without padding, stride 1 or 2 only");
-    STRAPS_REQUIRE(cout % 32 == 0 && cin % 64 == 0, "straps_conv_dgrad_x3f: need cout%%32==0 and cin%%64==0 (cin=%d cout=%d)", cin, cout);
+    const int ok = conv_geometry_check("straps_conv_dgrad_x3f", STRAPS_CONV_ROUTE_F32_1X1, STRAPS_CONV_KIND_DGRAD, batch, h, wdt, cin, cout, kh, kw, stride, pad);
+    if (ok != STRAPS_OK) return ok;
     STRAPS_REQUIRE(!addend_bits || addend, "straps_conv_dgrad_x3f: the ReLU bits mask an addend");
     STRAPS_REQUIRE(!bn_raw || (bn_mean && bn_invstd && bn_partials && (bn_out_bits || (bn_mask_scale && bn_mask_shift))),
                    "straps_conv_dgrad_x3f: the BatchNorm sums need raw, mean, invstd, partials, and the output's bits or mask scale / shift");
@@ -697,15 +604,11 @@ extern "C" int straps_conv_dgrad_x3f(const float* dy, const unsigned short* w3_c
         p.bnr_raw = bn_raw; p.bnr_out = nullptr; p.bnr_sc = bn_mask_scale; p.bnr_sh = bn_mask_shift; p.bnr_mean = bn_mean; p.bnr_invstd = bn_invstd;
         p.bnr_part = bn_partials; p.bnr_bits = bn_out_bits;
     }
-    return p.ncls ? dispatch_x3f(p, tile_cfg, (hipStream_t)stream) : STRAPS_OK;
+    return p.ncls ? dispatch_x3f("straps_conv_dgrad_x3f", p, tile_cfg, (hipStream_t)stream) : STRAPS_OK;
 }
 
-// M tiles (= BatchNorm-backward partial blocks) of straps_conv_dgrad_x3f for this geometry, all parity classes
+// M tiles (= BatchNorm-backward partial blocks) of straps_conv_dgrad_x3f with the fused BatchNorm sums and no addend, all parity classes
 extern "C" int straps_conv_dgrad_x3f_bn_blocks(int batch, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int tile_cfg) {
-    ConvP p;
-    p.x = nullptr; p.w = nullptr; p.xps = p.wps = 0;
-    if (!x3f_geometry_ok(kh, kw, pad) || !(stride == 1 || stride == 2)) return -1;
-    if (conv_dgrad_problem(p, nullptr, nullptr, batch, h, w, cin, cout, kh, kw, stride, pad) != STRAPS_OK) return -1;
-    p.y = reinterpret_cast<float*>(16); p.bnr_raw = reinterpret_cast<const float*>(16);      // (stand-ins: the tile rule looks at WHICH operands a launch has -- x3f_epilogue)
-    return x3f_blocks(p, tile_cfg);
+    return x3f_query_blocks("straps_conv_dgrad_x3f_bn_blocks", STRAPS_CONV_KIND_DGRAD, STRAPS_CONV_OP_Y | STRAPS_CONV_OP_BNR_RAW, batch, h, w, cin, cout, kh, kw, stride, pad,
+                            tile_cfg);
 }

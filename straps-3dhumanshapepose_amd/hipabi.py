@@ -148,6 +148,18 @@ WG_ROUTE_F32, WG_ROUTE_PLANES, WG_ROUTE_F32_1X1 = 0, 1, 2      # STRAPS_WG_ROUTE
 WG_FAMILIES = ('wgrad_f32', 'wgrad3_f32', 'wgrad_x3', 'wgrad3_x3', 'wgrad_x3f')      # STRAPS_WG_FAMILY_* by value
 
 
+class ConvPlanStruct(C.Structure):
+    """mirror of straps_conv_plan_t"""
+    _fields_ = [(n, C.c_int32) for n in ('family', 'tile', 'bm', 'bn', 'epilogue', 'abn', 'ncls')] + [('mt', C.c_int32 * 4), ('nt', C.c_int32), ('part_base', C.c_int32 * 4)] + \
+               [(n, C.c_int32) for n in ('blocks', 'grid_x', 'grid_y', 'threads', 'lds_bytes')]
+
+
+CONV_ROUTE_F32, CONV_ROUTE_PLANES, CONV_ROUTE_F32_1X1, CONV_ROUTE_BF16 = 0, 1, 2, 3      # STRAPS_CONV_ROUTE_*
+CONV_KIND_FWD, CONV_KIND_DGRAD = 0, 1                                                    # STRAPS_CONV_KIND_*
+CONV_FAMILIES = ('igemm_f32', 'x3', 'x3h', 'x3f', 'x3f_stream', 'bf16', 'bf16_halo')     # STRAPS_CONV_FAMILY_* by value
+CONV_OPS = {'y': 1, 'stats': 2, 'scale': 4, 'relu': 8, 'res': 16, 'res_bits': 32, 'bnr_raw': 64, 'bnr_out': 128, 'yplanes': 256, 'a_scale': 512}      # STRAPS_CONV_OP_*
+
+
 class RegressorDesc(C.Structure):
     """mirror of straps_regressor_desc_t"""
     _fields_ = [('layers', C.c_int32), ('in_channels', C.c_int32), ('ief_iters', C.c_int32), ('precision', C.c_int32)]
@@ -272,6 +284,8 @@ SIGNATURES = {
     'straps_conv_wgrad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     # the plan of a weight-gradient call (host arithmetic only; added without a version change)
     'straps_conv_wgrad_plan': (_I, [_I] * 10 + [C.POINTER(WgradPlanStruct)]),
+    # the plan of a forward / data-gradient convolution call (likewise)
+    'straps_conv_plan': (_I, [_I] * 13 + [C.POINTER(ConvPlanStruct)]),
     'straps_stem_wgrad_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     'straps_stem_wgrad': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'straps_stem_dgrad_weight_floats': (_Z, [_I]),

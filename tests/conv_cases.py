@@ -1,18 +1,20 @@
 """Test helper: the case tables of tests/test_gpu_conv_edges.py and a statement of WHICH KERNEL each case reaches.
 
-The convolution family (csrc/conv_x3.hip, conv_x3_lean.hip, conv_x3_kernels.h, conv_igemm.h, conv_x3f.hip, conv_wgrad_x3f.hip and conv_wgrad.hip
-with its plan, conv_wgrad_plan.h) picks its kernel instantiation from the geometry by size rules.  This module restates those rules in Python -- limited to what
-the tables need -- so that every case can say which instantiation and which epilogue form the library runs for it:
+The convolution family picks its kernel instantiation from the geometry by size rules, which live in two plans: csrc/conv_plan.h (forward and data
+gradient: conv.hip, conv_x3.hip, conv_x3_lean.hip, conv_x3f.hip, conv_bf16.hip launch from it) and csrc/conv_wgrad_plan.h (weight gradients: conv_wgrad.hip,
+conv_wgrad_x3f.hip).  This module restates those rules in Python -- limited to what the tables need -- so that every case can say which instantiation
+and which epilogue form the library runs for it:
 
-    pick_tile_x3 / halo_patch_slots / halo_choice / lean_epilogue_choice / x3_route        the plane kernels (forward and data gradient)
-    pick_tile_x3f / stream_bn / x3f_route                                                  the fp32-operand 1x1 route
+    pick_tile_x3 / halo_patch_slots / halo_choice / lean_epilogue_choice / x3_route        the plane kernels (conv_plan.h: conv_plan_x3)
+    pick_tile_x3f / stream_bn / stream_workgroups / x3f_route                              the fp32-operand 1x1 route (conv_plan_x3f)
+    x3_lds_bytes / x3f_lds_bytes / bf16_lds_bytes / launch_grid                            dynamic LDS and grid of an instantiation
     wgrad3_plan / wgrad_x3_route / wgrad_x3_block / wgrad_plan                             weight gradients on planes and on fp32 tensors
     wgrad_x3f_block / wgrad_x3f_plan                                                       weight gradient of the fp32-operand route
     pick_tile_bf16 / bf16_refusal / bf16_route / bf16_nchunks                              the single-product bf16 inference route (conv_bf16.hip;
                                                                                            the cases of tests/test_gpu_conv_bf16_edges.py)
 
-tests/test_conv_cases_cpu.py holds the restatement to everything the built library reveals without a launch (the block-count, workspace and route
-queries) for every case, and asserts that the tables together reach every instantiation the product library can dispatch to (REQUIRED below; the
+tests/test_conv_cases_cpu.py holds the restatement to the plans the built library shows without a launch (straps_conv_plan, straps_conv_wgrad_plan:
+instantiation, row tile, partial blocks, grid, LDS; and the block-count, workspace and route queries that wrap them) for every case, and asserts that the tables together reach every instantiation the product library can dispatch to (REQUIRED below; the
 ones no network layer reaches are in UNREACHABLE with the reason).  A later change of a size rule that moves a case off its kernel fails there.
 
 An instantiation is named by a tuple:
@@ -180,15 +182,32 @@ def x3_route(p, tile_cfg, ops):
 
 def x3_stat_blocks(B, H, W, cin, cout, k, stride, pad, tile_cfg):
     """straps_conv_x3_stat_blocks"""
-    p = fwd_problem(B, H, W, cin, cout, k, stride, pad)
-    if halo_choice(p, tile_cfg):
-        return p.cls[0].M // 128
-    return -(-p.cls[0].M // pick_tile_x3(tile_cfg, p.cls[0].M, cout)[1])
+    return x3_route(fwd_problem(B, H, W, cin, cout, k, stride, pad), tile_cfg, {'y', 'stats'})[2]
 
 
 def dgrad_x3_bn_blocks(B, H, W, cin, cout, k, stride, pad, tile_cfg):
     """straps_conv_dgrad_x3_bn_blocks"""
     return x3_route(dgrad_problem(B, H, W, cin, cout, k, stride, pad), tile_cfg, {'y', 'res', 'bnr_raw'})[2]
+
+
+# (wave rows, wave columns, ring stages) of the plane tiles and (.., patch slots, patch buffers) of the halo forms: conv_plan.h kX3Tile / kX3Halo
+X3_WAVES_STAGES = {1: (4, 2, 3), 2: (2, 2, 2), 3: (2, 2, 3), 4: (4, 2, 2), 5: (2, 2, 3), 7: (2, 2, 3), 8: (2, 2, 3), 9: (4, 2, 3), 10: (2, 2, 3), 11: (2, 2, 2), 12: (4, 2, 2)}
+X3_HALO_FORMS = {1: (128, 2, 2, 3, 208, 2), 2: (64, 2, 2, 3, 272, 2), 3: (64, 2, 2, 2, 272, 1)}      # bn first
+
+
+def x3_lds_bytes(inst):
+    """dynamic LDS and threads of a plane instantiation: stages x three planes x (BM + BN) rows of 32 bf16; the halo forms hold patch buffers of `slots`
+    pixels in the A rows' place"""
+    if inst[0] == 'x3h':
+        bn, wm, wn, nst, slots, pbuf = X3_HALO_FORMS[inst[1]]
+        return (pbuf * 3 * slots + nst * 3 * bn) * 32 * 2, 64 * wm * wn
+    wm, wn, nst = X3_WAVES_STAGES[inst[1]]
+    return nst * 3 * (X3_BM[inst[1]] + X3_BN[inst[1]]) * 32 * 2, 64 * wm * wn
+
+
+def launch_grid(p, bm, bn):
+    """(grid x, grid y) of the tile kernels: one grid row per class, as wide as the largest class"""
+    return max(-(-c.M // bm) for c in p.cls) * (p.Cout // bn), len(p.cls)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -251,10 +270,21 @@ def x3f_route(p, tile_cfg, ops):
     return ('x3f', cfg, epi, abn), bm, blocks
 
 
+def x3f_lds_bytes(p, inst):
+    """-> (dynamic LDS, threads, (grid x, grid y)) of an fp32-operand instantiation"""
+    if inst[0] == 'x3f_stream':
+        bn = inst[1]
+        bm = 64 if bn == 256 else 128
+        wgs, _ = stream_workgroups(p, bn)
+        return stream_lds_bytes(bm, bn, 2, bn == 256, p.Cin), 64 * 2 * (2 if bn == 64 else 4), (wgs * (p.Cout // bn), 1)
+    bm = 64 if inst[1] == 2 else 128
+    return 2 * 3 * (bm + 64) * 32 * 2, 256, launch_grid(p, bm, 64)
+
+
 def x3f_stat_blocks(B, H, W, cin, cout, k, stride, pad, tile_cfg):
     if not (k == 1 and pad == 0):
         return -1
-    return x3f_route(fwd_problem(B, H, W, cin, cout, k, stride, pad), tile_cfg, {'y'})[2]
+    return x3f_route(fwd_problem(B, H, W, cin, cout, k, stride, pad), tile_cfg, {'y', 'stats'})[2]
 
 
 def dgrad_x3f_bn_blocks(B, H, W, cin, cout, k, stride, pad, tile_cfg):
@@ -460,6 +490,14 @@ def bf16_route(p, cfg):
         cfg = pick_tile_bf16(p.cls[0].M, p.Cout)
     assert bf16_refusal(p, cfg) is None, (p, cfg)
     return ('bf16', cfg)
+
+
+def bf16_lds_bytes(cfg):
+    """(dynamic LDS, threads): the plane kernels' formula with PL chunks of one plane in the three planes' place"""
+    pl, nst, bm, bn = BF16_PL[cfg], BF16_NST[cfg], BF16_BM[cfg], BF16_BN[cfg]
+    if cfg in BF16_HALO:
+        return ((2 if cfg == 9 else 1) * pl * BF16_HALO[cfg] + nst * pl * bn) * 32 * 2, 256
+    return nst * pl * (bm + bn) * 32 * 2, 512 if bm == 256 else 256
 
 
 def bf16_nchunks(p, cfg):
@@ -691,9 +729,46 @@ def conv_case_id(c):
     return 'B%d_%dx%d_%dto%d_k%ds%d_cfg%d' % c
 
 
-def reached():
-    """every instantiation the tables reach -> {instantiation: [case ids]}, from the lists test_gpu_conv_edges.py itself iterates over: FWD_RUN,
-    dgrad_run(case) with its twin flags, X3F_FWD_FORMS, X3F_DGRAD_FORMS, and one plan per weight-gradient case"""
+def _problem(kind, g):
+    return (fwd_problem if kind == 'fwd' else dgrad_problem)(*g)
+
+
+def restated_inst(route, kind, g, cfg, ops):
+    """the instantiation a launch reaches by the restatement.  route: 'x3' / 'x3f' / 'bf16'; kind: 'fwd' / 'dgrad'; g = (B, H, W, Cin, Cout, k, stride, pad)"""
+    p = _problem(kind, g)
+    return {'x3': x3_route, 'x3f': x3f_route}[route](p, cfg, ops)[0] if route != 'bf16' else bf16_route(p, cfg)
+
+
+def launches():
+    """every launch of the forward / data-gradient tables of tests/test_gpu_conv_edges.py and test_gpu_conv_bf16_edges.py, from the lists the GPU files
+    themselves iterate over (FWD_RUN, dgrad_run(case), X3F_FWD_FORMS, X3F_DGRAD_FORMS; every admitted bf16 configuration):
+    -> [(case id, route, kind, g, tile_cfg, ops, whether a lean launch runs again under its twin's tile_cfg)]"""
+    out = []
+    for c in FWD_EXPLICIT + FWD_AUTO:
+        B, H, W, ci, co, k, s, cfg = c
+        out += [('fwd:' + conv_case_id(c), 'x3', 'fwd', (B, H, W, ci, co, k, s, pad_of(k)), cfg, fwd_ops(v), True) for v in FWD_RUN]
+    for c in FWD_PLANES:
+        B, H, W, ci, co, k, s, cfg = c
+        out += [('fwdp:' + conv_case_id(c), 'x3', 'fwd', (B, H, W, ci, co, k, s, pad_of(k)), cfg, fwd_ops(v), False) for v in ('planes', 'planes_only')]
+    for c in DGRAD_EXPLICIT + DGRAD_S2_SMALL + DGRAD_AUTO:
+        B, H, W, ci, co, k, s, cfg = c
+        out += [('dgrad:' + conv_case_id(c), 'x3', 'dgrad', (B, H, W, ci, co, k, s, pad_of(k)), cfg, DGRAD_FORMS[form], with_twin) for form, with_twin in dgrad_run(c)]
+    for c in X3F_FWD:
+        B, H, W, ci, co, s, cfg = c
+        out += [('x3f_fwd:' + x3f_case_id(c), 'x3f', 'fwd', (B, H, W, ci, co, 1, s, 0), cfg, ops, False) for ops in X3F_FWD_FORMS.values()]
+    for c in X3F_DGRAD:
+        B, H, W, ci, co, s, cfg = c
+        out += [('x3f_dgrad:' + x3f_case_id(c), 'x3f', 'dgrad', (B, H, W, ci, co, 1, s, 0), cfg, ops, False) for ops in X3F_DGRAD_FORMS.values()]
+    for c in BF16_EXPLICIT:
+        p = bf16_problem(c)
+        out += [('bf16:' + bf16_case_id(c), 'bf16', 'fwd', c + (c[5] // 2,), cfg, {'y', 'yplanes'}, False) for cfg in BF16_TILES if bf16_refusal(p, cfg) is None]
+    out += [('bf16:' + bf16_case_id(c) + '_cfg0', 'bf16', 'fwd', c + (c[5] // 2,), 0, {'y', 'yplanes'}, False) for c in BF16_AUTO]
+    return out
+
+
+def reached(inst_of=restated_inst):
+    """every instantiation the tables reach -> {instantiation: [case ids]}: launches() -- a lean plane launch again under its twin's tile_cfg --
+    through inst_of (the restatement, or the library's plan: tests/test_conv_cases_cpu.py), and one plan per weight-gradient case"""
     got = {}
 
     def add(inst, cid):
@@ -701,50 +776,17 @@ def reached():
         if cid not in got[inst]:
             got[inst].append(cid)
 
-    for c in FWD_EXPLICIT + FWD_AUTO:
-        B, H, W, ci, co, k, s, cfg = c
-        p = fwd_problem(B, H, W, ci, co, k, s, pad_of(k))
-        for v in FWD_RUN:
-            inst = x3_route(p, cfg, fwd_ops(v))[0]
-            add(inst, 'fwd:' + conv_case_id(c))
-            if inst[2]:
-                add(x3_route(p, twin_cfg(p, cfg, fwd_ops(v)), fwd_ops(v))[0], 'fwd:' + conv_case_id(c))
-    for c in FWD_PLANES:
-        B, H, W, ci, co, k, s, cfg = c
-        for v in ('planes', 'planes_only'):
-            add(x3_route(fwd_problem(B, H, W, ci, co, k, s, pad_of(k)), cfg, fwd_ops(v))[0], 'fwdp:' + conv_case_id(c))
-    for c in DGRAD_EXPLICIT + DGRAD_S2_SMALL + DGRAD_AUTO:
-        B, H, W, ci, co, k, s, cfg = c
-        p = dgrad_problem(B, H, W, ci, co, k, s, pad_of(k))
-        for form, with_twin in dgrad_run(c):
-            ops = DGRAD_FORMS[form]
-            inst = x3_route(p, cfg, ops)[0]
-            add(inst, 'dgrad:' + conv_case_id(c))
-            if inst[2] and with_twin:
-                add(x3_route(p, twin_cfg(p, cfg, ops), ops)[0], 'dgrad:' + conv_case_id(c))
-    for c in X3F_FWD:
-        B, H, W, ci, co, s, cfg = c
-        p = fwd_problem(B, H, W, ci, co, 1, s, 0)
-        for ops in X3F_FWD_FORMS.values():
-            add(x3f_route(p, cfg, ops)[0], 'x3f_fwd:' + x3f_case_id(c))
-    for c in X3F_DGRAD:
-        B, H, W, ci, co, s, cfg = c
-        p = dgrad_problem(B, H, W, ci, co, 1, s, 0)
-        for ops in X3F_DGRAD_FORMS.values():
-            add(x3f_route(p, cfg, ops)[0], 'x3f_dgrad:' + x3f_case_id(c))
+    for cid, route, kind, g, cfg, ops, with_twin in launches():
+        inst = inst_of(route, kind, g, cfg, ops)
+        add(inst, cid)
+        if route == 'x3' and inst[2] and with_twin:
+            add(inst_of(route, kind, g, twin_cfg(_problem(kind, g), cfg, ops), ops), cid)
     for c in WGRAD_HALO + WGRAD_TAP:
         add(wgrad_plan(*c, pad_of(c[5])).inst, 'wgrad:B%d_%dx%d_%dto%d_k%ds%d' % c)
     for c in WGRAD_F32:
         add(wgrad_plan(*c, pad_of(c[5]), planes=False).inst, 'wgrad_f32:B%d_%dx%d_%dto%d_k%ds%d' % c)
     for c in WGRAD_X3F:
         add(wgrad_x3f_plan(*c).inst, 'wgrad_x3f:B%d_%dx%d_%dto%d_s%d_bn%d' % c)
-    for c in BF16_EXPLICIT:          # (tests/test_gpu_conv_bf16_edges.py: every admitted configuration of every case)
-        p = bf16_problem(c)
-        for cfg in BF16_TILES:
-            if bf16_refusal(p, cfg) is None:
-                add(bf16_route(p, cfg), 'bf16:' + bf16_case_id(c))
-    for c in BF16_AUTO:
-        add(bf16_route(bf16_problem(c), 0), 'bf16:' + bf16_case_id(c) + '_cfg0')
     return got
 
 

@@ -159,8 +159,11 @@ def test_the_library_plan_is_the_restated_plan_field_by_field(lib):
     assert lib.straps_conv_wgrad_plan(hipabi.WG_ROUTE_F32, 1, 8, 8, 64, 64, 3, 3, 1, 1, None) == 1
 
 
-def test_the_tables_reach_every_instantiation_the_product_library_dispatches_to():
-    got = K.reached()
+def test_the_tables_reach_every_instantiation_the_product_library_dispatches_to(lib):
+    """the reached set is the LIBRARY's: every forward / data-gradient launch of the tables is named by straps_conv_plan (the weight gradients are held to
+    straps_conv_wgrad_plan above), and the restatement names the same ones"""
+    got = K.reached(lambda route, kind, g, cfg, ops: _plan_inst(_conv_plan(lib, route, kind, g, cfg, ops)))
+    assert got == K.reached()
     missing = [i for i in K.REQUIRED if i not in got and i not in K.UNREACHABLE]
     assert not missing, 'no case reaches %s' % missing
     assert all(i in K.REQUIRED or i[0] == 'wgrad_x3' for i in K.UNREACHABLE)
@@ -308,6 +311,214 @@ def test_weight_gradient_tables_hold_the_plans_they_are_named_for():
     assert set(fb) == {(256, 64), (64, 256), (256, 128), (128, 256), (128, 128), (64, 64)} and all({1, 31, 33, 129} <= m for m in fb.values())
     assert 'empty' in {K.last_split_state(K.wgrad_x3f_plan(*c)) for c in K.WGRAD_X3F}
     assert {K.wgrad_plan(*c, K.pad_of(c[5]), planes=False).inst for c in K.WGRAD_F32} == {('wgrad3_f32',), ('wgrad_f32', 64), ('wgrad_f32', 128)}
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------
+# the launch plan of the forward / data-gradient convolutions (csrc/conv_plan.h) against the restatement
+
+ROUTES = {'x3': hipabi.CONV_ROUTE_PLANES, 'x3f': hipabi.CONV_ROUTE_F32_1X1, 'bf16': hipabi.CONV_ROUTE_BF16}
+KINDS = {'fwd': hipabi.CONV_KIND_FWD, 'dgrad': hipabi.CONV_KIND_DGRAD}
+
+
+def _conv_plan(lib, route, kind, g, cfg, ops):
+    """straps_conv_plan for g = (B, H, W, Cin, Cout, k, stride, pad) -> the raw struct"""
+    B, H, W, ci, co, k, s, pad = g
+    out = hipabi.ConvPlanStruct()
+    rc = lib.straps_conv_plan(ROUTES[route], KINDS[kind], sum(hipabi.CONV_OPS[o] for o in ops), B, H, W, ci, co, k, k, s, pad, cfg, C.byref(out))
+    assert rc == 0, (route, kind, g, cfg, ops, lib.straps_last_error())
+    return out
+
+
+def _plan_inst(out):
+    """the instantiation a plan names, in conv_cases.py's terms"""
+    fam = hipabi.CONV_FAMILIES[out.family]
+    if fam in ('x3', 'x3h'):
+        return (fam, out.tile, out.epilogue)
+    if fam == 'x3f':
+        return (fam, out.tile, out.epilogue, bool(out.abn))
+    if fam == 'x3f_stream':
+        return (fam, out.bn, out.epilogue, bool(out.abn))
+    assert fam in ('bf16', 'bf16_halo') and out.epilogue == 3 and (fam == 'bf16_halo') == (out.tile in K.BF16_HALO)
+    return ('bf16', out.tile)
+
+
+def _restated_launch(route, kind, g, cfg, ops):
+    """-> (instantiation, bm, blocks, (grid x, grid y), LDS bytes, threads) by conv_cases.py"""
+    p = K._problem(kind, g)
+    if route == 'bf16':
+        inst = K.bf16_route(p, cfg)
+        bm, bn = K.BF16_BM[inst[1]], K.BF16_BN[inst[1]]
+        return (inst, bm, -(-p.cls[0].M // bm), K.launch_grid(p, bm, bn)) + K.bf16_lds_bytes(inst[1])
+    inst, bm, blocks = (K.x3_route if route == 'x3' else K.x3f_route)(p, cfg, ops)
+    if route == 'x3f':
+        lds, threads, grid = K.x3f_lds_bytes(p, inst)
+        return inst, bm, blocks, grid, lds, threads
+    bn = K.X3_HALO_FORMS[inst[1]][0] if inst[0] == 'x3h' else K.X3_BN[inst[1]]
+    return (inst, bm, blocks, K.launch_grid(p, bm, bn)) + K.x3_lds_bytes(inst)
+
+
+def _hold_plan_to_restatement(lib, route, kind, g, cfg, ops):
+    want = _restated_launch(route, kind, g, cfg, ops)
+    out = _conv_plan(lib, route, kind, g, cfg, ops)
+    got = (_plan_inst(out), out.bm, out.blocks, (out.grid_x, out.grid_y), out.lds_bytes, out.threads)
+    assert got == want, (route, kind, g, cfg, sorted(ops), got, want)
+    # the partial blocks are the M tiles of the classes, one class after the other
+    p = K._problem(kind, g)
+    assert out.ncls == len(p.cls) and list(out.mt)[:out.ncls] == [-(-c.M // out.bm) for c in p.cls] and sum(out.mt) == out.blocks
+    assert list(out.part_base)[:out.ncls] == [sum(list(out.mt)[:i]) for i in range(out.ncls)] and out.nt * out.bn == p.Cout
+    return out
+
+
+def test_the_library_plan_names_the_restated_launch_for_every_case(lib):
+    """straps_conv_plan == x3_route / x3f_route / bf16_route for every launch of the forward / data-gradient tables -- instantiation, row tile, partial
+    blocks, grid, LDS bytes, threads; the streaming kernel's grid is stream_workgroups' -- under the case's own tile_cfg with every operand set the GPU
+    files run it with, under its twin's, and (the fp32-operand route has no twin) under every tile_cfg of that route"""
+    n = 0
+    for cid, route, kind, g, cfg, ops, with_twin in K.launches():
+        out = _hold_plan_to_restatement(lib, route, kind, g, cfg, ops)
+        n += 1
+        if route == 'x3' and out.epilogue:
+            twin = K.twin_cfg(K._problem(kind, g), cfg, ops)
+            t = _hold_plan_to_restatement(lib, route, kind, g, twin, ops)
+            assert (t.family, t.tile, t.bm, t.bn, t.epilogue) == (out.family, out.tile, out.bm, out.bn, 0), (cid, twin)
+        if route == 'x3f':
+            for c5 in (0, 1, 2, 5):
+                _hold_plan_to_restatement(lib, route, kind, g, c5, ops)
+    assert n > 1800
+
+
+def _m_map(M):
+    return (1, 1, M)
+
+
+T_EDGES = (127, 128, 255, 256, 511, 512)
+
+
+def test_the_library_plan_is_the_restated_one_around_every_threshold_of_the_rules(lib):
+    """the same comparison at the rules' thresholds (arithmetic only: the sizes are free), and every legacy block-count / tile-choice query is the plan's
+    field for the operand set include/straps_hip.h states for it"""
+    n = 0
+    # plane routes: 128x128-tile equivalents per class = 127 / 128 / 255 / 256 / 511 / 512, one class (a forward) and four (a stride-2 gradient whose dx
+    # has 4 t x 128 pixels), one-tap and nine-tap filters, 128- and 256-wide against the cout % 128 != 0 branch (64, 192); with and without the halo kernel
+    for t, k, wide, cfg in itertools.product(T_EDGES, (1, 3), (128, 256, 64, 192), (0, 256, 512, 512 | 1024, 64)):
+        rows = -(-t // (wide // 128)) if wide % 128 == 0 else t          # (t counts tiles of 128 columns: a 256-wide layer needs half the rows)
+        for (B, H, W) in ((1, rows, 128), (1, 1, rows * 128 + 1), (rows, 16, 8)):
+            g = (B, H, W, 32, wide, k, 1, K.pad_of(k))
+            for ops in (K.fwd_ops('raw_stats'), K.fwd_ops('fused')):
+                _hold_plan_to_restatement(lib, 'x3', 'fwd', g, cfg, ops)
+            assert lib.straps_conv_x3_stat_blocks(B, H, W, 32, wide, k, k, 1, K.pad_of(k), cfg) == _conv_plan(lib, 'x3', 'fwd', g, cfg, {'y', 'stats'}).blocks
+            n += 1
+        g = (1, 2 * rows, 256, wide, 32, k, 2, K.pad_of(k))                   # dx: 512 x rows pixels in four parity classes
+        for form in ('addend', 'bn_out', 'bn_bits'):
+            _hold_plan_to_restatement(lib, 'x3', 'dgrad', g, cfg, K.DGRAD_FORMS[form])
+        assert lib.straps_conv_dgrad_x3_bn_blocks(*g[:5], k, k, 2, K.pad_of(k), cfg) == _conv_plan(lib, 'x3', 'dgrad', g, cfg, {'y', 'res', 'bnr_raw'}).blocks
+    # the size classes above are really on both sides of each threshold
+    for t, want in zip(T_EDGES, (3, 7, 7, 5, 5, 12)):
+        assert _plan_inst(_conv_plan(lib, 'x3', 'fwd', (1, t, 128, 32, 128, 1, 1, 0), 0, {'y', 'stats'})) == ('x3', want, 1)
+    for t, want in zip(T_EDGES, (3, 11, 11, 9, 9, 12)):
+        assert _plan_inst(_conv_plan(lib, 'x3', 'dgrad', (1, 2 * t, 256, 128, 32, 1, 2, 0), 0, K.DGRAD_FORMS['addend'])) == ('x3', want, 0)
+    # fp32-operand route: 128x64 tiles of a class = 511 / 512 (shared epilogue: never the streaming kernel), one class and four
+    for t, co, cfg in itertools.product((511, 512), (64, 128, 192), (0, 1, 2, 5)):
+        rows = -(-t // (co // 64))
+        for ops in K.X3F_FWD_FORMS.values():
+            _hold_plan_to_restatement(lib, 'x3f', 'fwd', (1, rows, 128, 64, co, 1, 1, 0), cfg, ops)
+        for ops in K.X3F_DGRAD_FORMS.values():
+            _hold_plan_to_restatement(lib, 'x3f', 'dgrad', (1, 2 * rows, 256, co, 64, 1, 2, 0), cfg, ops)
+            _hold_plan_to_restatement(lib, 'x3f', 'dgrad', (1, rows, 128, co, 64, 1, 1, 0), cfg, ops)
+        n += 1
+    assert [_plan_inst(_conv_plan(lib, 'x3f', 'fwd', (1, t, 128, 64, 64, 1, 1, 0), 0, K.X3F_FWD_FORMS['eval']))[:2] for t in (511, 512)] == [('x3f', 2), ('x3f', 1)]
+    # ... and the streaming rule's bound M >= 4 x 128 x (256 / N tiles) at M - 1 / M, for each width of its tile and an N-tile count that does not divide 256
+    for ci, co, sbn in ((64, 64, 64), (64, 128, 128), (64, 256, 256), (64, 1024, 256), (128, 1024, 128), (64, 192, 64), (128, 64, 64)):
+        bound = 4 * 128 * (256 // (co // sbn))
+        for M, stream in ((bound - 1, False), (bound, True)):
+            for ops in K.X3F_FWD_FORMS.values():
+                out = _hold_plan_to_restatement(lib, 'x3f', 'fwd', _m_map(M) + (ci, co, 1, 1, 0), 0, ops)
+                lean = 'scale' not in ops
+                assert (hipabi.CONV_FAMILIES[out.family] == 'x3f_stream') == (stream and lean) and (not (stream and lean) or out.bn == sbn), (ci, co, M, sorted(ops))
+            for name, ops in K.X3F_DGRAD_FORMS.items():
+                out = _hold_plan_to_restatement(lib, 'x3f', 'dgrad', _m_map(M) + (co, ci, 1, 1, 0), 0, ops)
+                assert (hipabi.CONV_FAMILIES[out.family] == 'x3f_stream') == stream and out.epilogue == (2 if name == 'full' else 1), (ci, co, M, name)      # (a plain stride-1 gradient is the lean FORWARD form)
+            g = _m_map(M) + (ci, co, 1, 1, 0)
+            assert lib.straps_conv_x3f_stat_blocks(*g[:5], 1, 1, 1, 0, 0) == _conv_plan(lib, 'x3f', 'fwd', g, 0, {'y', 'stats'}).blocks
+            g = _m_map(M) + (co, ci, 1, 1, 0)
+            assert lib.straps_conv_dgrad_x3f_bn_blocks(*g[:5], 1, 1, 1, 0, 0) == _conv_plan(lib, 'x3f', 'dgrad', g, 0, {'y', 'bnr_raw'}).blocks
+            n += 1
+    # the geometry grid of the block-count test above: the legacy queries are the plan's fields there too
+    maps = [(1, 1, 1), (1, 3, 43), (2, 8, 8), (4, 4, 8), (1, 4, 64), (8, 16, 16), (4, 32, 32), (2, 64, 64), (1, 128, 127), (1, 128, 128), (1, 129, 128), (2, 128, 128),
+            (4, 128, 129), (8, 128, 128), (1, 255, 257), (3, 91, 241), (16, 64, 64), (64, 16, 16), (128, 8, 8), (512, 8, 8), (32, 32, 32)]
+    for (B, H, W), (ci, co), (k, s), cfg in itertools.product(maps, ((64, 64), (64, 128), (128, 64), (256, 256), (128, 512)), ((3, 1), (3, 2), (1, 1), (1, 2)),
+                                                            (0, 1, 3, 5, 6, 9, 12, 13, 256, 512, 1536, 64)):
+        g = (B, H, W, ci, co, k, s, K.pad_of(k))
+        assert lib.straps_conv_x3_stat_blocks(B, H, W, ci, co, k, k, s, g[7], cfg) == _hold_plan_to_restatement(lib, 'x3', 'fwd', g, cfg, {'y', 'stats'}).blocks
+        assert lib.straps_conv_dgrad_x3_bn_blocks(B, H, W, ci, co, k, k, s, g[7], cfg) == _hold_plan_to_restatement(lib, 'x3', 'dgrad', g, cfg, {'y', 'res', 'bnr_raw'}).blocks
+        if k == 1 and cfg in (0, 1, 5, 6):
+            assert lib.straps_conv_x3f_stat_blocks(B, H, W, ci, co, 1, 1, s, 0, cfg) == _hold_plan_to_restatement(lib, 'x3f', 'fwd', g, cfg, {'y', 'stats'}).blocks
+            if s == 1:
+                assert lib.straps_conv_dgrad_x3f_bn_blocks(B, H, W, ci, co, 1, 1, s, 0, cfg) == _hold_plan_to_restatement(lib, 'x3f', 'dgrad', g, cfg, {'y', 'bnr_raw'}).blocks
+            else:
+                assert lib.straps_conv_dgrad_x3f_bn_blocks(B, H, W, ci, co, 1, 1, s, 0, cfg) == _conv_plan(lib, 'x3f', 'dgrad', g, cfg, {'y', 'bnr_raw'}).blocks
+        n += 1
+    # bf16 route: 255 / 256 / 511 / 512 tile equivalents, M one short of and one past a multiple of 128, cout % 128
+    for M, co, (k, s) in itertools.product((1, 127, 128, 129, 255 * 128, 255 * 128 + 1, 256 * 128 - 1, 256 * 128, 256 * 128 + 1, 511 * 128, 511 * 128 + 1, 512 * 128, 1024 * 128),
+                                           (64, 128, 192, 256, 320, 512), ((1, 1), (3, 1))):
+        for (B, H, W) in ((1, 1, M), (1, M, 1)) + (((M // 128, 16, 8),) if M % 128 == 0 else ()):
+            out = _hold_plan_to_restatement(lib, 'bf16', 'fwd', (B, H, W, 64, co, k, s, k // 2), 0, {'y', 'yplanes'})
+            assert lib.straps_conv_bf16_tile_choice(B, H, W, 64, co, k, k, s, k // 2) == out.tile
+            n += 1
+    # fp32 implicit GEMM: straps_conv_stat_blocks is the plan's `blocks` (the fp32 rule reads no operand)
+    for (B, H, W), (ci, co), k, cfg in itertools.product(maps, ((64, 64), (64, 128), (256, 256), (128, 512)), (1, 3), (0, 1, 2, 3, 4, 16, 20, 32, 36)):
+        out = hipabi.ConvPlanStruct()
+        assert lib.straps_conv_plan(hipabi.CONV_ROUTE_F32, hipabi.CONV_KIND_FWD, 3, B, H, W, ci, co, k, k, 1, K.pad_of(k), cfg, C.byref(out)) == 0
+        assert hipabi.CONV_FAMILIES[out.family] == 'igemm_f32' and lib.straps_conv_stat_blocks(B, H, W, co, k * k * ci, cfg) == out.blocks == -(-B * H * W // out.bm)
+        assert (out.grid_x, out.grid_y, out.threads) == (out.blocks * (co // out.bn), 1, 256)
+        assert out.lds_bytes == (2 * (out.bm + out.bn) * 36 * 4 if (cfg & 48) == 16 else 2 * (out.bm + out.bn) * 32 * 4)
+        n += 1
+    assert n > 7000
+
+
+def test_the_library_plan_refuses_what_the_entry_points_refuse(lib):
+    """every refusal is STRAPS_EINVAL with its reason; a NULL `out` is refused"""
+    out = hipabi.ConvPlanStruct()
+    F, X, O, H = hipabi.CONV_ROUTE_F32, hipabi.CONV_ROUTE_PLANES, hipabi.CONV_ROUTE_F32_1X1, hipabi.CONV_ROUTE_BF16
+
+    def refused(why, route, kind, geom, cfg=0):
+        assert lib.straps_conv_plan(route, kind, 1, *geom, cfg, C.byref(out)) == 1, (why, route, kind, geom)
+        err = lib.straps_last_error().decode()
+        assert err.startswith('straps_conv_plan: ') and why in err, (why, err)
+
+    ok = (2, 8, 8, 64, 64, 3, 3, 1, 1)
+    assert lib.straps_conv_plan(X, 0, 1, *ok, 0, None) == 1 and b'null pointer' in lib.straps_last_error()
+    refused('unknown route', 4, 0, ok)
+    refused('unknown route', -1, 0, ok)
+    refused('kind is 0', X, 2, ok)
+    refused('forward only', H, 1, ok)
+    for route in (F, X, O, H):
+        refused('empty input', route, 0, (0, 8, 8, 64, 64, 1, 1, 1, 0))
+    for route in (F, X):
+        refused('cin%32==0 and cout%64==0', route, 0, (2, 8, 8, 48, 64, 3, 3, 1, 1))
+        refused('cin%32==0 and cout%64==0', route, 0, (2, 8, 8, 32, 96, 3, 3, 1, 1))
+        refused('bad filter geometry', route, 0, (2, 8, 8, 64, 64, 5, 5, 1, 2))
+        refused('bad filter geometry', route, 0, (2, 8, 8, 64, 64, 3, 3, 0, 1))
+        refused('cout%32==0 and cin%64==0', route, 1, (2, 8, 8, 32, 64, 3, 3, 1, 1))
+        refused('stride must be 1 or 2', route, 1, (2, 8, 8, 64, 64, 3, 3, 3, 1))
+        refused('unsupported filter geometry', route, 1, (2, 8, 8, 64, 64, 3, 3, 1, 3))
+    refused('1x1 filters without padding only', O, 0, ok)
+    refused('1x1 filters without padding only', O, 0, (2, 8, 8, 64, 64, 1, 1, 1, 1))
+    refused('1x1 filters without padding, stride 1 or 2 only', O, 1, ok)
+    refused('1x1 filters without padding, stride 1 or 2 only', O, 1, (2, 8, 8, 64, 64, 1, 1, 3, 0))
+    refused('cin%64==0 and cout%64==0', H, 0, (2, 8, 8, 32, 64, 3, 3, 1, 1))
+    refused('tile_cfg must be in [0, 10]', H, 0, ok, 11)
+    refused('tile_cfg must be in [0, 10]', H, 0, ok, -1)
+    # the bf16 route's configuration refusals: every (case, configuration) the restatement refuses, with its reason
+    n = 0
+    for c in K.BF16_EXPLICIT:
+        p = K.bf16_problem(c)
+        for cfg in K.BF16_TILES:
+            why = K.bf16_refusal(p, cfg)
+            if why is not None:
+                refused('tile_cfg %d: %s' % (cfg, why), H, 0, _bf16_geo(c), cfg)
+                n += 1
+    assert n > 100
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------------

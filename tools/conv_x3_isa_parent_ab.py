@@ -1,10 +1,11 @@
-"""Instruction-stream A/B of the bf16x3 plane kernels against a parent revision: conv_x3_kernels.h is templated on a plane count (PL, last template
-parameter; PL = 0 = the bf16x3 kernels) for the single-product bf16 route, and the shared epilogue on its output plane count -- the existing
-instantiations must compile to the SAME instructions.  conv_x3.hip and conv_x3_lean.hip of the working tree and of REV (git archive) are compiled with
-`hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S`; directives, comments, labels' translation-unit ids and the trailing template argument of
-the new parameter (ELi0E in the mangled names) are normalised away, and what remains is diffed per kernel.  CPU only.
+"""Instruction-stream A/B of the forward / data-gradient convolution kernels against a parent revision: a change of the host side (the launch plan,
+the dispatchers, the launchers) must leave every kernel's instructions as they were, and the set of instantiations too.  conv.hip, conv_x3.hip,
+conv_x3_lean.hip, conv_x3f.hip and conv_bf16.hip of the working tree and of REV (git archive) are compiled with
+`hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S`; directives, comments and labels other than basic blocks are dropped, the function's number in the
+translation unit is taken out of the basic-block labels (.LBB<n>_<k>: it follows the order of instantiation, which a host-side change moves; likewise .Lpost_getpc<n>), and what
+remains is diffed per kernel under its mangled name as it stands.  CPU only.
 
-    python tools/conv_x3_isa_parent_ab.py [--rev HEAD] [--out profiles/conv_x3_isa_parent_diff.txt]
+    python tools/conv_x3_isa_parent_ab.py [--rev HEAD] [--out profiles/conv_plan_isa_parent_diff.txt]
 """
 import argparse
 import difflib
@@ -16,7 +17,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = 'straps-3dhumanshapepose_amd'
-SOURCES = ('conv_x3.hip', 'conv_x3_lean.hip')
+SOURCES = ('conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_x3f.hip', 'conv_bf16.hip')
 
 
 def asm(csrc, src, out):
@@ -26,50 +27,53 @@ def asm(csrc, src, out):
     return open(out).read()
 
 
-def kernels(text, strip_pl):
-    """kernel name -> normalised instruction lines (strip_pl: drop the trailing PL = 0 argument of the working tree's names)"""
+def kernels(text):
+    """kernel name -> instruction lines"""
     out, cur = {}, None
     for line in text.splitlines():
         m = re.match(r'^(_Z\S+):', line)
         if m:
-            cur = re.sub(r'ELi0EEEvNS_5ConvPE$', 'EEEvNS_5ConvPE', m.group(1)) if strip_pl else m.group(1)
+            cur = m.group(1)
             out[cur] = []
             continue
         if cur is None:
             continue
         s = line.split(';')[0].rstrip()
         if not s.strip() or s.lstrip().startswith('.') or re.match(r'^\s*\S+:$', s) and 'BB' not in s:
-            if s.strip().startswith('.Lfunc_end'):
+            if s.strip().startswith(('.Lfunc_end', '.size')):
                 cur = None
             continue
-        out[cur].append(s)
+        out[cur].append(re.sub(r'\.Lpost_getpc\d+', '.Lpost_getpc', re.sub(r'\.LBB\d+_', '.LBB_', s)))
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rev', default='HEAD', help='parent revision (before the change is committed: HEAD; afterwards: HEAD~1)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'conv_x3_isa_parent_diff.txt'))
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'conv_plan_isa_parent_diff.txt'))
     a = ap.parse_args()
     rev = subprocess.run(['git', 'rev-parse', '--short=12', a.rev], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
-    lines = ['bf16x3 plane kernels: instruction streams of the working tree against %s (hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S)' % rev]
-    total = 0
+    lines = ['forward / data-gradient convolution kernels: instruction streams of the working tree against %s (hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S)' % rev]
+    total = moved = 0
     with tempfile.TemporaryDirectory() as tmp:
         arch = subprocess.run(['git', 'archive', a.rev, PKG + '/csrc', 'include'], cwd=ROOT, capture_output=True, check=True).stdout
         subprocess.run(['tar', '-x', '-C', tmp], input=arch, check=True)
         for src in SOURCES:
-            old = kernels(asm(os.path.join(tmp, PKG, 'csrc'), src, os.path.join(tmp, 'old_' + src + '.s')), False)
-            new = kernels(asm(os.path.join(ROOT, PKG, 'csrc'), src, os.path.join(tmp, 'new_' + src + '.s')), True)
-            assert set(old) == set(new), (src, sorted(set(old) ^ set(new)))
-            for k in sorted(old):
+            old = kernels(asm(os.path.join(tmp, PKG, 'csrc'), src, os.path.join(tmp, 'old_' + src + '.s')))
+            new = kernels(asm(os.path.join(ROOT, PKG, 'csrc'), src, os.path.join(tmp, 'new_' + src + '.s')))
+            for k in sorted(set(old) | set(new)):
+                if k not in old or k not in new:
+                    moved += 1
+                    lines.append('%s  %-100s %6d instructions  only in the %s' % (src, k, len(old.get(k, new.get(k))), 'parent' if k in old else 'working tree'))
+                    continue
                 d = list(difflib.unified_diff(old[k], new[k], lineterm='', n=0))
                 total += len(d)
-                lines.append('%s  %-90s %6d instructions  %s' % (src, k, len(old[k]), 'identical' if not d else '%d diff lines' % len(d)))
+                lines.append('%s  %-100s %6d instructions  %s' % (src, k, len(old[k]), 'identical' if not d else '%d diff lines' % len(d)))
                 lines += d[:40]
-    lines.append('TOTAL diff lines: %d' % total)
+    lines.append('TOTAL diff lines: %d; instantiations only on one side: %d' % (total, moved))
     open(a.out, 'w').write('\n'.join(lines) + '\n')
     print('\n'.join(lines[-3:]))
-    sys.exit(1 if total else 0)
+    sys.exit(1 if total or moved else 0)
 
 
 if __name__ == '__main__':
