@@ -900,6 +900,36 @@ int straps_silhouette_counts(const uint8_t* pred, const uint8_t* target, int32_t
 size_t straps_wp_silhouette_workspace_bytes(long long batch, int nverts);
 int straps_wp_silhouette(const float* verts, const int32_t* faces, const float* cam_wp, uint8_t* mask,
                          void* workspace, long long batch, int nverts, int nfaces, int wh, void* stream);
+/* ---- the head of a validation step (train/train_synthetic_otf_rendering.py:313-348 + metrics/train_loss_and_metrics_tracker.py:118-213;
+ * csrc/val.hip; added without a version change) ----
+ * Forward only: the prediction heads, the five task losses of losses/multi_task_loss.py (reduction 'mean') and the tracker's eleven
+ * metric sums of one batch, added to a device-resident accumulator -- a whole validation pass costs one device-to-host copy at its end.
+ * Inputs as straps_loss_fwd_bwd's: pred_verts / tgt_verts [B][nverts][3], pred_joints [B][90][3] (the 17 COCO and the 14 H36M-LSP joints
+ * are read through the index maps), est [B][ld_est] = (cam s, tx, ty | 144 pose | 10 shape | padding), pred_rot / tgt_rot [B][24][3][3],
+ * tgt_joints2d [B][17][2] in pixels, tgt_joints3d [B][14][3], tgt_shape [B][10], log_vars [5] in the kernel's task order (verts, joints2D,
+ * joints3D, shape_params, pose_params).  pred_reposed / tgt_reposed [B][nverts][3] may BOTH be NULL.
+ * Every sum is taken in fp64 from the fp32 inputs; every stored fp32 value is rounded once.
+ *   batch_out [12]     : the layout of straps_loss_fwd_bwd's loss_out -- total, five weighted task losses, five raw MSEs, visible-joint
+ *                        count; the joints2D entries (and the total) are NaN when no target joint is visible, as nn.MSELoss on nothing.
+ *   per_sample [B][11] : per sample, in the order of metrics.BatchMetrics.KEYS: the three error sums of straps_point_metrics (raw,
+ *                        scale-and-translation corrected, Procrustes aligned) for the vertices, the first two for the reposed vertices
+ *                        (0 without them), the three for the 14 joints; the sum of squares of the shape difference; of the rotation
+ *                        difference; the sum over the 17 joints of the pixel distance after undo_keypoint_normalisation, visible or not.
+ *                        A row depends on its own sample only.
+ *   acc [24] (doubles) : exactly one addition per slot and call: acc[0..10] += batch * (double)batch_out[0..10] (the tracker's
+ *                        loss.item() * num_inputs), acc[11] += batch_out[11], acc[12 + k] += sum over b ascending of
+ *                        (double)per_sample[b][k], acc[23] += batch.  The caller zeroes it once.
+ * Each of the three may be NULL; at least one must not be.  The values written do not depend on which of the others are given.
+ * workspace: straps_val_head_workspace_bytes(batch) bytes, 8-byte aligned.  nverts >= 3, ld_est >= 157, img_wh > 0.
+ * Two launches on `stream`; no atomics, so the result does not depend on scheduling.  Arguments are checked before any HIP call
+ * (STRAPS_EINVAL, straps_last_error() names the argument); nothing is allocated or synchronised: the call can be captured into a hipGraph. */
+size_t straps_val_head_workspace_bytes(long long batch);
+int straps_val_head(const float* pred_verts, const float* pred_reposed, const float* pred_joints,
+                    const float* est, int ld_est, const float* pred_rot, const float* tgt_verts,
+                    const float* tgt_reposed, const float* tgt_joints2d, const float* tgt_joints3d,
+                    const float* tgt_shape, const float* tgt_rot, const float* log_vars,
+                    float* batch_out, float* per_sample, double* acc, void* workspace,
+                    long long batch, int nverts, int img_wh, void* stream);
 /* torch.optim.Adam defaults (run_train.py:200-201) over one flat fp32 buffer:
  * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps);
  * grad_scale multiplies g first (1/world_size after a sum all-reduce).  step_dev (optional device

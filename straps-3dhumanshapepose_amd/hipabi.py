@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'conv_wgrad.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
-           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'render.hip', 'measure.hip']
+           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'render.hip', 'measure.hip', 'val.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -335,6 +335,9 @@ SIGNATURES = {
     'straps_silhouette_counts': (_I, [_P, _P, _P, _L, _L, _P]),
     'straps_wp_silhouette_workspace_bytes': (_Z, [_L, _I]),
     'straps_wp_silhouette': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    # the forward-only head of a validation step: losses + metric sums into a device accumulator (csrc/val.hip; added without a version change)
+    'straps_val_head_workspace_bytes': (_Z, [_L]),
+    'straps_val_head': (_I, [_P, _P, _P, _P, _I] + [_P] * 12 + [_L, _I, _I, _P]),
     # test-time fitting to 2-D keypoints, all iterations in one launch (csrc/fit.hip; added without a version change)
     'straps_fit_keypoints': (_I, [C.POINTER(FitModelStruct), C.POINTER(FitOptsStruct)] + [_P] * 11 + [_L, _P]),
     # the silhouette term of test-time fitting and the update step of a composed fit loop (csrc/silfit.hip; added without a version change)
