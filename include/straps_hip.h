@@ -1195,8 +1195,8 @@ int straps_render_mesh(const float* verts, const int32_t* faces, const int32_t* 
 /* ---- body measurements of a batch of meshes (csrc/measure.hip; added without a version change) -------------------------------------
  * Volume, surface area, extent along a direction, planar girths and lengths along anchor points, n_meas of them per body, in one call.
  * Vertices and points are read as fp32; every product, sum, division and square root is done in double; each result is rounded to float
- * once.  out [B][n_meas].  Not differentiable; girths are plane sections, not tape-measure (convex hull) girths; planes and directions
- * are the same for every body of the batch (T-pose bodies: no per-body normals).
+ * once.  out [B][n_meas].  Not differentiable.  A GIRTH is the length of the plane section, and planes and directions are the same for
+ * every body of the batch; tape-measure (convex hull) girths and per-body plane normals: straps_measure_tape below.
  *   anchor       a names vertex a of the body when 0 <= a < nverts, points[b][a - nverts] when nverts <= a < nverts + n_points
  *                (points [B][n_points][3], may be NULL when n_points == 0); -1 means "none".
  *   selected     face f is selected iff its three indices lie in [0, nverts) and (part_mask == 0, or face_parts[f] < 32 and bit
@@ -1236,6 +1236,65 @@ size_t straps_measure_workspace_bytes(long long batch, int nverts, int nfaces, i
 int straps_measure_mesh(const float* verts, const float* points, const int32_t* faces, const uint8_t* face_parts,
         const straps_measure_t* meas, float* out, void* workspace, long long batch, int nverts, int n_points, int nfaces,
         int n_meas, void* stream);
+
+/* ---- tape-measure girths, per-body planes (csrc/measure_tape.hip; added without a version change) -----------------------------------
+ * What a tape laid round the body in a plane reads: the perimeter of the CONVEX HULL of the plane section (a tape spans the spine groove
+ * and the gap between two thighs; the section length follows them), n_meas of them per body in one call; and the plane's normal may be
+ * taken per body from two of its anchors, which is what a posed mesh needs.  out [B][n_meas] float.
+ *   anchors, selected faces   exactly as straps_measure_mesh states them above: anchor a is vertex a or points[b][a - nverts]; a face is
+ *                selected iff its three indices lie in [0, nverts) and (part_mask == 0, or face_parts[f] < 32 and that bit is set).
+ *   arithmetic   vertices and points are read as fp32; every product, sum, division and square root is double; each result is rounded
+ *                to float once.
+ *   plane        through o = anchor[0] (required).  Normal n = dir (as double) when anchor[1] == -1; otherwise n = A1 - A0, the
+ *                difference of THAT body's anchors anchor[1] and anchor[0], each component subtracted in double (dir is not read).
+ *                n is not normalised for the side test.  A normal that is zero or has a non-finite component cuts nothing: value 0,
+ *                count 0.
+ *   section points   GIRTH's: d_i = (n_x (p_i - o)_x + n_y (p_i - o)_y) + n_z (p_i - o)_z; vertex i is positive iff d_i >= 0 (a NaN is
+ *                not).  A selected face is CUT iff its three sides are not all equal; then one vertex a stands alone on its side and the
+ *                two edges (a, b), (a, c) to the following corners in the face's cyclic order give the face's two section points
+ *                x = p_a + t (p_b - p_a), t = d_a / (d_a - d_b), and x' likewise with c.
+ *   SECTION      the sum over the cut faces of |x - x'|: GIRTH's value, now with a per-body plane.  0 when nothing is cut.
+ *   HULL         Q is the multiset of all section points, two per cut face (a mesh edge that two selected faces share is crossed twice
+ *                and appears twice: expected).  Q is expressed in an orthonormal basis (u, v) of the plane built in double from n:
+ *                    k = the index of the component of n with the smallest magnitude (the first such on a tie);
+ *                    a = e_k x n, i.e. k = 0: (0, -n_z, n_y), k = 1: (n_z, 0, -n_x), k = 2: (-n_y, n_x, 0);   u = a / sqrt(a . a);
+ *                    w = n x u;   v = w / sqrt(w . w);      q = (u . (x - o), v . (x - o)), dots summed as (x + y) + z.
+ *                The value is the perimeter of the convex hull of Q (invariant under the choice of basis up to rounding): 0 when Q is
+ *                empty or all its points coincide; twice the segment's length when Q is collinear (the tape goes there and back); NaN
+ *                iff some section point of that (body, measurement) is non-finite, or its count exceeds `capacity` (below).
+ *   counts       [B][n_meas] int32 or NULL: the number of section points, 2 x the cut faces, for either kind; always the full count,
+ *                whatever `capacity` is.
+ *   capacity     the number of section points per (body, measurement) that the workspace holds: 0 means the worst case 2 * nfaces,
+ *                otherwise 2 <= capacity <= 2 * nfaces.  A HULL row whose count exceeds it is NaN; SECTION stores nothing and is
+ *                unaffected; `counts` tells the caller what happened.
+ * Limits, as straps_measure_mesh's: 1 <= n_meas <= 32, 1 <= nverts <= 2^20, 0 <= n_points <= 64, 1 <= batch, batch * n_meas < 2^31,
+ * part_mask != 0 needs face_parts; here 1 <= nfaces <= 715827882 and kind is STRAPS_TAPE_HULL or STRAPS_TAPE_SECTION.  anchor[0], and
+ * anchor[1] unless it is -1, lie in [0, nverts + n_points).  Every failure is STRAPS_EINVAL before any HIP call and names the argument.
+ * `meas` is a HOST array, copied by value into the launches.
+ * workspace (8-byte aligned), with cap = capacity, or 2 * nfaces when capacity == 0:
+ *     straps_measure_tape_workspace_bytes = batch * n_meas * 8 * (2 + 2 * cap) bytes
+ * -- per (body, measurement) two doubles (count, section length) and cap (u, v) pairs -- and 0 for an argument outside the limits above
+ * (nverts is not an argument of the size) or a size of 2^62 bytes or more.
+ * Two launches on `stream`.  collect: a workgroup per (body, measurement) walks the faces in index order, 256 per trip; a cut face takes
+ * its slot from a ballot / popcount prefix in its wave plus the counts of the waves and trips before it, so slot order is face order,
+ * without atomics; the SECTION length is added per thread in face order, then in a fixed tree.  hull (launched only when a HULL is
+ * asked for): a workgroup per (body, measurement) marches the two monotone chains -- from the lexicographic minimum of (u, v), among the
+ * points lexicographically greater than the current one the most clockwise, the farther of collinear ones, by a fixed-tree reduction
+ * on coordinates alone, to the lexicographic maximum; the same way back -- and adds the edge lengths in chain order.  Every step moves
+ * strictly forward in lexicographic order, so a chain ends after at most `count` steps whatever rounding does to an orientation test.
+ * No allocation, no synchronisation, no floating-point atomics, nothing read that the call has not written; capturable;
+ * bit-reproducible; a row depends on that body's inputs alone (same bits alone or in a batch; a NaN body leaves the others untouched). */
+enum { STRAPS_TAPE_HULL = 0, STRAPS_TAPE_SECTION = 1 };
+typedef struct {
+    int32_t kind;
+    int32_t anchor[2];
+    float dir[3];
+    uint32_t part_mask;
+} straps_tape_t;
+size_t straps_measure_tape_workspace_bytes(long long batch, int nfaces, int n_meas, int capacity);
+int straps_measure_tape(const float* verts, const float* points, const int32_t* faces, const uint8_t* face_parts,
+        const straps_tape_t* meas, float* out, int32_t* counts, void* workspace, long long batch, int nverts, int n_points,
+        int nfaces, int n_meas, int capacity, void* stream);
 
 #ifdef __cplusplus
 }

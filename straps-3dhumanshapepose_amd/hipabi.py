@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'conv_wgrad.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
-           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'render.hip', 'measure.hip', 'val.hip']
+           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'render.hip', 'measure.hip', 'val.hip', 'measure_tape.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -199,6 +199,15 @@ MEASURE_FACES_PER_BLOCK, MEASURE_VERTS_PER_BLOCK = 512, 2048      # csrc/measure
 MEASURE_MAX, MEASURE_MAX_POINTS = 32, 64
 
 
+class TapeStruct(C.Structure):
+    """mirror of straps_tape_t"""
+    _fields_ = [('kind', C.c_int32), ('anchor', C.c_int32 * 2), ('dir', C.c_float * 3), ('part_mask', C.c_uint32)]
+
+
+TAPE_HULL, TAPE_SECTION = range(2)      # STRAPS_TAPE_*
+MEASURE_TAPE_FACES_PER_BLOCK = 256      # csrc/measure_tape.hip: faces of one trip of a collect workgroup (where the slot prefix crosses a trip)
+
+
 _P, _I, _L, _F, _Z, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes); must list every symbol of include/straps_hip.h (tests/test_abi.py checks)
@@ -351,6 +360,9 @@ SIGNATURES = {
     # body measurements: volume, area, extent, girths, lengths (csrc/measure.hip; added without a version change)
     'straps_measure_workspace_bytes': (_Z, [_L, _I, _I, _I]),
     'straps_measure_mesh': (_I, [_P, _P, _P, _P, C.POINTER(MeasureStruct), _P, _P, _L, _I, _I, _I, _I, _P]),
+    # tape-measure girths (convex hull of the section) and per-body planes (csrc/measure_tape.hip; added without a version change)
+    'straps_measure_tape_workspace_bytes': (_Z, [_L, _I, _I, _I]),
+    'straps_measure_tape': (_I, [_P, _P, _P, _P, C.POINTER(TapeStruct), _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
     'straps_comm_unique_id': (_I, [_P]),
     'straps_comm_init_rank': (_I, [_P, _I, _I, C.POINTER(C.c_void_p)]),
     'straps_comm_destroy': (_I, [_P]),

@@ -1,19 +1,26 @@
 """Body measurements of a batch of meshes on the device: height, volume, surface area, girths and limb lengths (csrc/measure.hip,
-straps_measure_mesh; include/straps_hip.h states the definitions).
+straps_measure_mesh), and tape-measure girths with the plane's normal given once or taken per body (csrc/measure_tape.hip,
+straps_measure_tape); include/straps_hip.h states the definitions.
 
     measurer = BodyMeasurer.from_smpl(smpl).to(device)            # the tables of the model, default_measurements()
     m = measurer(vertices, joints)                                # {'values': [B,M] float32, 'height': [B], 'volume': [B], ...}
     m = predictor.measure(out, measurer)                          # the predicted body in the T-pose
+    tape = BodyMeasurer.from_smpl(smpl, tape_measurements()).to(device)      # what a tape reads: convex hull of the plane section
+    posed = BodyMeasurer.from_smpl(smpl, posed_measurements()).to(device)    # limb girths, planes perpendicular to the bone of EACH body
+    m = predictor.measure(out, posed, posed=True)                 # the predicted body as posed
 
-A measurement is a spec made by one of the helpers below; `measurements` is a dict name -> spec (or a sequence of (name, spec)), at most 32.
-An anchor is an int (a vertex id) or ('joint', j): row j of the `joints` given to the call.  `parts` is an iterable of part labels (0..31)
-of the per-face table `face_parts` (this package's labels, synthetic_smpl.JOINT_TO_PART: 1 / 2 left / right arm, 3 head, 4 / 5 left / right leg,
-6 torso); None: every face.
+A measurement is a spec made by one of the helpers below; `measurements` is a dict name -> spec (or a sequence of (name, spec)), at most 32,
+old and new kinds in any mix.  An anchor is an int (a vertex id) or ('joint', j): row j of the `joints` given to the call.  `parts` is an
+iterable of part labels (0..31) of the per-face table `face_parts` (this package's labels, synthetic_smpl.JOINT_TO_PART: 1 / 2 left / right
+arm, 3 head, 4 / 5 left / right leg, 6 torso); None: every face.
+
+`girth` is the length of the plane section, which follows concavities; `tape_girth` is the perimeter of the section's convex hull, which spans
+them as a tape does (the two agree on a convex section); `section_girth` is `girth` with the new plane options.  The plane of the two new
+helpers has either a `normal` shared by the batch or `toward`: a second anchor, the normal being that anchor minus the first one on each
+body -- a plane perpendicular to a bone, wherever the pose has put it.
 
 All arithmetic is double on fp32 vertices, rounded to float once; results are bit-reproducible and a body's row depends on that body alone.
-OUT OF SCOPE: gradients of measurements (the call is not differentiable); tape-measure girths (a girth here is the length of the plane
-section, which follows concavities; a tape spans them: convex hull of the section); measurements on posed meshes with per-body plane
-normals (planes and directions are shared by the batch, which suits bodies in one pose: the T-pose).
+The calls are not differentiable.
 """
 import collections
 import ctypes as C
@@ -27,6 +34,9 @@ from . import config, hipabi
 
 Spec = collections.namedtuple('Spec', ('kind', 'anchors', 'direction', 'parts'))
 KIND_NAMES = ('volume', 'area', 'extent', 'girth', 'path')
+# Spec.kind of the specs that go to straps_measure_tape: TAPE_KIND_BASE + hipabi.TAPE_*; never a kind of straps_measure_mesh
+TAPE_KIND_BASE = 100
+TAPE_KINDS = (TAPE_KIND_BASE + hipabi.TAPE_HULL, TAPE_KIND_BASE + hipabi.TAPE_SECTION)
 
 
 def _anchor(a, what):
@@ -85,6 +95,25 @@ def path(*anchors):
     return Spec(hipabi.MEASURE_PATH, tuple(_anchor(a, 'measure.path') for a in anchors), (0.0, 0.0, 0.0), None)
 
 
+def _tape_spec(what, kind, anchor, normal, parts, toward):
+    if (normal is None) == (toward is None):
+        raise ValueError('%s: give exactly one of normal= (shared by the batch) and toward= (a second anchor: the normal per body)' % what)
+    if toward is None:
+        return Spec(TAPE_KIND_BASE + kind, (_anchor(anchor, what),), _direction(normal, what), _parts(parts, what))
+    return Spec(TAPE_KIND_BASE + kind, (_anchor(anchor, what), _anchor(toward, what)), (0.0, 0.0, 0.0), _parts(parts, what))
+
+
+def tape_girth(anchor, normal=None, parts=None, toward=None):
+    """what a tape reads: the perimeter of the convex hull of the section of the selected faces with the plane through `anchor`; its normal
+    is `normal`, or on each body the anchor `toward` minus `anchor`"""
+    return _tape_spec('measure.tape_girth', hipabi.TAPE_HULL, anchor, normal, parts, toward)
+
+
+def section_girth(anchor, normal=None, parts=None, toward=None):
+    """length of the section (what `girth` gives) with the plane of `tape_girth`: `normal`, or `toward` for a normal per body"""
+    return _tape_spec('measure.section_girth', hipabi.TAPE_SECTION, anchor, normal, parts, toward)
+
+
 def default_measurements():
     """The default set, anchored at SMPL's public joint numbering (0 pelvis, 1 / 2 hips, 3 spine1, 4 / 5 knees, 7 / 8 ankles, 9 spine3, 16 / 17
     shoulders, 18 / 19 elbows, 20 / 21 wrists) and this package's part labels, for T-pose bodies (y up, arms along x):
@@ -114,11 +143,72 @@ def default_measurements():
         ('shoulder_breadth', path(j(16), j(17)))])
 
 
+def tape_measurements():
+    """The seven girths of default_measurements() as tape girths, for T-pose bodies (y up, arms along x):
+
+        chest_tape_girth, waist_tape_girth       planes through joints 9 and 3, normal y, torso
+        hip_tape_girth                           plane through joint 0, normal y, torso AND both leg parts: the tape spans the two thighs
+        thigh_tape_girth_l / _r                  normal y through the knee joint (4 / 5), the leg part of that side
+        upper_arm_tape_girth_l / _r              normal x through the elbow joint (18 / 19), the arm part of that side
+
+    These positions are UNTUNED on the real model, as those of default_measurements() are and for the same reason: only the synthetic
+    stand-in was available, whose triangle soup is not a body surface.  Check them on your model before relying on absolute numbers."""
+    j = lambda k: ('joint', k)
+    y, x = (0.0, 1.0, 0.0), (1.0, 0.0, 0.0)
+    return collections.OrderedDict([
+        ('chest_tape_girth', tape_girth(j(9), y, parts=(6,))), ('waist_tape_girth', tape_girth(j(3), y, parts=(6,))),
+        ('hip_tape_girth', tape_girth(j(0), y, parts=(4, 5, 6))),
+        ('thigh_tape_girth_l', tape_girth(j(4), y, parts=(4,))), ('thigh_tape_girth_r', tape_girth(j(5), y, parts=(5,))),
+        ('upper_arm_tape_girth_l', tape_girth(j(18), x, parts=(1,))), ('upper_arm_tape_girth_r', tape_girth(j(19), x, parts=(2,)))])
+
+
+def posed_measurements():
+    """Limb tape girths for bodies in ANY pose: every plane passes through a joint and is perpendicular to the bone towards the neighbouring
+    joint of that body (`toward=`), so it turns with the limb:
+
+        posed_thigh_girth_l / _r         through the knee (4 / 5) toward the hip joint (1 / 2), leg part
+        posed_calf_girth_l / _r          through the ankle (7 / 8) toward the knee (4 / 5), leg part
+        posed_upper_arm_girth_l / _r     through the elbow (18 / 19) toward the shoulder (16 / 17), arm part
+        posed_forearm_girth_l / _r       through the wrist (20 / 21) toward the elbow (18 / 19), arm part
+
+    Give the call the posed joints (Predictor.measure(out, measurer, posed=True) does).  These positions are UNTUNED on the real model, as
+    those of default_measurements() are: a plane through a joint is where the part ends or bends, and a plane further along the bone needs a
+    vertex anchor of your model."""
+    j = lambda k: ('joint', k)
+    return collections.OrderedDict([
+        ('posed_thigh_girth_l', tape_girth(j(4), toward=j(1), parts=(4,))), ('posed_thigh_girth_r', tape_girth(j(5), toward=j(2), parts=(5,))),
+        ('posed_calf_girth_l', tape_girth(j(7), toward=j(4), parts=(4,))), ('posed_calf_girth_r', tape_girth(j(8), toward=j(5), parts=(5,))),
+        ('posed_upper_arm_girth_l', tape_girth(j(18), toward=j(16), parts=(1,))), ('posed_upper_arm_girth_r', tape_girth(j(19), toward=j(17), parts=(2,))),
+        ('posed_forearm_girth_l', tape_girth(j(20), toward=j(18), parts=(1,))), ('posed_forearm_girth_r', tape_girth(j(21), toward=j(19), parts=(2,)))])
+
+
+def tape_structs(specs, nverts):
+    """-> (hipabi.TapeStruct array, number of points the specs read) for specs of tape_girth / section_girth"""
+    arr = (hipabi.TapeStruct * len(specs))()
+    n_points = 0
+    for q, s in zip(arr, specs):
+        if s.kind not in TAPE_KINDS:
+            raise ValueError('measure.tape_structs: %r is not a spec of measure.tape_girth / section_girth' % (s,))
+        q.kind = s.kind - TAPE_KIND_BASE
+        q.anchor[:] = [-1, -1]
+        for i, a in enumerate(s.anchors):
+            if isinstance(a, tuple):
+                q.anchor[i] = nverts + a[1]
+                n_points = max(n_points, a[1] + 1)
+            else:
+                q.anchor[i] = a
+        q.dir[:] = s.direction
+        q.part_mask = sum(1 << p for p in s.parts) if s.parts else 0
+    return arr, n_points
+
+
 def measure_structs(specs, nverts):
     """-> (hipabi.MeasureStruct array, number of points the specs read): ('joint', j) anchors resolve to nverts + j"""
     arr = (hipabi.MeasureStruct * len(specs))()
     n_points = 0
     for q, s in zip(arr, specs):
+        if s.kind not in range(len(KIND_NAMES)):      # (a tape spec goes to straps_measure_tape: tape_structs)
+            raise ValueError('measure.measure_structs: %r is not a spec of measure.volume / area / extent / girth / path' % (s,))
         q.kind = s.kind
         q.anchor[:] = [-1, -1, -1, -1]
         for i, a in enumerate(s.anchors):
@@ -135,9 +225,12 @@ def measure_structs(specs, nverts):
 class BodyMeasurer(nn.Module):
     """Measures a batch of meshes of one topology (see the module docstring).  faces [F,3] and face_parts [F] (None: no spec may name parts) are
     held as buffers; faces=None loads config.SMPL_FACES_PATH, and then the part table from the reference's texture files, as NMRRenderer does.
-    measurements=None: default_measurements()."""
+    measurements=None: default_measurements().  Specs of tape_girth / section_girth go to straps_measure_tape, the others to
+    straps_measure_mesh (a call without specs of one sort is not made); `values` holds the columns in the order of `names`.  tape_capacity:
+    the section points per (body, tape measurement) that the workspace holds, None: the worst case, 2 * faces.  A tape girth of a body
+    that cuts more is NaN; measure_counts tells how many there were."""
 
-    def __init__(self, faces=None, face_parts=None, measurements=None):
+    def __init__(self, faces=None, face_parts=None, measurements=None, tape_capacity=None):
         super().__init__()
         name = 'BodyMeasurer'
         if faces is None:
@@ -168,25 +261,48 @@ class BodyMeasurer(nn.Module):
             raise RuntimeError("%s: measurement names must be distinct and none may be 'values' (got %r)" % (name, self.names))
         for n, s in items:
             if not isinstance(s, Spec):
-                raise RuntimeError('%s: measurement %r is not a spec of measure.volume / area / extent / girth / path (got %r)' % (name, n, s))
+                raise RuntimeError('%s: measurement %r is not a spec of measure.volume / area / extent / girth / path / tape_girth / section_girth (got %r)'
+                                   % (name, n, s))
             if s.parts and face_parts is None:
                 raise RuntimeError('%s: measurement %r selects parts %r but no face_parts table was given' % (name, n, s.parts))
-            if s.kind in (hipabi.MEASURE_VOLUME, hipabi.MEASURE_AREA, hipabi.MEASURE_GIRTH) and faces.shape[0] == 0:
+            if s.kind not in range(len(KIND_NAMES)) and s.kind not in TAPE_KINDS:
+                raise RuntimeError('%s: measurement %r has the unknown kind %r' % (name, n, s.kind))
+            if s.kind in (hipabi.MEASURE_VOLUME, hipabi.MEASURE_AREA, hipabi.MEASURE_GIRTH) + TAPE_KINDS and faces.shape[0] == 0:
                 raise RuntimeError('%s: measurement %r reads faces but the face table is empty' % (name, n))
         self.needs_joints = max([a[1] + 1 for s in self.specs for a in s.anchors if isinstance(a, tuple)] or [0])
+        # columns of `values` that each library call fills, in the order of `names`
+        self.tape_columns = tuple(i for i, s in enumerate(self.specs) if s.kind in TAPE_KINDS)
+        self.mesh_columns = tuple(i for i, s in enumerate(self.specs) if s.kind not in TAPE_KINDS)
+        self.tape_names = tuple(self.names[i] for i in self.tape_columns)
+        if tape_capacity is not None:
+            if isinstance(tape_capacity, (bool, float)) or int(tape_capacity) != tape_capacity or not 2 <= int(tape_capacity) <= 2 * max(1, faces.shape[0]):
+                raise RuntimeError('%s: tape_capacity is None (the worst case) or a number of section points in 2..2 * faces = %d (got %r)'
+                                   % (name, 2 * faces.shape[0], tape_capacity))
+            tape_capacity = int(tape_capacity)
+        self.tape_capacity = tape_capacity
         self._structs = {}
+        self._tape_structs = {}
 
     @classmethod
-    def from_smpl(cls, smpl, measurements=None):
+    def from_smpl(cls, smpl, measurements=None, tape_capacity=None):
         """the face and part tables of an SMPL module (its `.faces` / `.face_parts`: the model file's, or the synthetic model's)"""
         if getattr(smpl, 'faces', None) is None:
             raise RuntimeError('BodyMeasurer.from_smpl: the SMPL model carries no faces; pass faces= (and face_parts=) to BodyMeasurer')
-        return cls(smpl.faces, getattr(smpl, 'face_parts', None), measurements)
+        return cls(smpl.faces, getattr(smpl, 'face_parts', None), measurements, tape_capacity)
 
     @hipabi.on_tensor_device
     def measure_arrays(self, vertices, joints=None):
         """vertices [B,N,3], joints None or [B,J,3] (fp32 GPU) -> values [B,M] float32.  Never synchronises; runs on the current stream;
         capturable."""
+        return self._measure(vertices, joints, False)
+
+    @hipabi.on_tensor_device
+    def measure_counts(self, vertices, joints=None):
+        """-> int32 [B, n_tape]: the section points (2 x the cut faces) of every tape_girth / section_girth, in the order of `tape_names`,
+        whatever tape_capacity is: a count above it is a NaN tape girth.  Runs the tape call alone; never synchronises."""
+        return self._measure(vertices, joints, True)
+
+    def _measure(self, vertices, joints, want_counts):
         name = 'BodyMeasurer'
         hipabi.require_gpu_tensor(vertices, 'vertices', torch.float32)
         hipabi.require_gpu_tensor(self.faces, name + ' buffers (call .to(device))', torch.int32)
@@ -206,17 +322,46 @@ class BodyMeasurer(nn.Module):
             for a in s.anchors:
                 if not isinstance(a, tuple) and a >= N:
                     raise RuntimeError('%s: measurement %r is anchored at vertex %d, the mesh has %d' % (name, n, a, N))
-        if N not in self._structs:
-            self._structs[N] = measure_structs(self.specs, N)
-        arr, n_points = self._structs[N]
         vertices = vertices.detach().contiguous()
         L = hipabi.lib()
-        M, F = len(self.specs), self.faces.shape[0]
-        out = torch.empty(B, M, device=vertices.device, dtype=torch.float32)
-        ws = torch.empty(L.straps_measure_workspace_bytes(B, N, F, M) // 8, device=vertices.device, dtype=torch.float64)
-        hipabi.check(L.straps_measure_mesh(hipabi.ptr(vertices), hipabi.ptr(points), hipabi.ptr(self.faces) if F else None, hipabi.ptr(self.face_parts), arr,
-                                           hipabi.ptr(out), hipabi.ptr(ws), B, N, n_points, F, M, hipabi.stream_ptr()), 'straps_measure_mesh')
-        return out
+        F = self.faces.shape[0]
+        # both calls get the SAME points tensor, [B, needs_joints, 3]: its row count is the stride by which they find a body's points, whatever the
+        # highest joint that the specs of one call alone read
+        n_points = self.needs_joints
+        out = tape_out = counts = None
+        if self.mesh_columns and not want_counts:
+            if N not in self._structs:
+                self._structs[N] = measure_structs([self.specs[i] for i in self.mesh_columns], N)
+            arr = self._structs[N][0]
+            M = len(self.mesh_columns)
+            out = torch.empty(B, M, device=vertices.device, dtype=torch.float32)
+            ws = torch.empty(L.straps_measure_workspace_bytes(B, N, F, M) // 8, device=vertices.device, dtype=torch.float64)
+            hipabi.check(L.straps_measure_mesh(hipabi.ptr(vertices), hipabi.ptr(points), hipabi.ptr(self.faces) if F else None, hipabi.ptr(self.face_parts), arr,
+                                               hipabi.ptr(out), hipabi.ptr(ws), B, N, n_points, F, M, hipabi.stream_ptr()), 'straps_measure_mesh')
+        if self.tape_columns:
+            if N not in self._tape_structs:
+                self._tape_structs[N] = tape_structs([self.specs[i] for i in self.tape_columns], N)
+            arr = self._tape_structs[N][0]
+            T, cap = len(self.tape_columns), self.tape_capacity or 0
+            ws_bytes = L.straps_measure_tape_workspace_bytes(B, F, T, cap)
+            if not ws_bytes:
+                raise RuntimeError('%s: no tape workspace for batch %d, %d faces, %d tape measurements, capacity %d' % (name, B, F, T, cap))
+            tape_out = torch.empty(B, T, device=vertices.device, dtype=torch.float32)
+            if want_counts:
+                counts = torch.empty(B, T, device=vertices.device, dtype=torch.int32)
+            ws = torch.empty(ws_bytes // 8, device=vertices.device, dtype=torch.float64)
+            hipabi.check(L.straps_measure_tape(hipabi.ptr(vertices), hipabi.ptr(points), hipabi.ptr(self.faces), hipabi.ptr(self.face_parts), arr,
+                                               hipabi.ptr(tape_out), hipabi.ptr(counts), hipabi.ptr(ws), B, N, n_points, F, T, cap, hipabi.stream_ptr()),
+                         'straps_measure_tape')
+        if want_counts:
+            return counts if counts is not None else torch.empty(B, 0, device=vertices.device, dtype=torch.int32)
+        if tape_out is None:
+            return out
+        if out is None:
+            return tape_out
+        src = {i: out[:, k] for k, i in enumerate(self.mesh_columns)}
+        src.update({i: tape_out[:, k] for k, i in enumerate(self.tape_columns)})
+        return torch.stack([src[i] for i in range(len(self.specs))], 1)
 
     def forward(self, vertices, joints=None):
         """-> {'values': [B,M] float32, name: [B] (a view of its column), ...} in the order of `self.names`"""

@@ -10,7 +10,8 @@ These are the PREDICT-side semantics, not the training-side ones of image_utils.
 is not clamped to the frame (what sticks out reads as zero, and the joints are shifted by the unclamped corner), and the heat maps are
 the numpy ones (float64 joints truncated to int16, a float64 Gaussian).  The detectors, pad_to_square and the resize of the RGB image are
 not part of this package; of the visualisation, the two rendered pictures of predict_3D.py:169-178 are (`Predictor.render`).
-`Predictor.measure` turns the predicted T-pose body into height, volume, girths and limb lengths (measure.py).
+`Predictor.measure` turns the predicted T-pose body into height, volume, girths and limb lengths, and with posed=True measures the body as
+posed, for tape girths whose planes follow the limbs (measure.py).
 """
 import numpy as np
 import torch
@@ -176,11 +177,16 @@ class Predictor:
                     'reposed': renderer(out['reposed_vertices'], cam.expand(B, 3).contiguous(), rotation=rx180)}
 
     @hipabi.on_tensor_device
-    def measure(self, out, measurer):
+    def measure(self, out, measurer, posed=False):
         """body measurements of the prediction: `out` a result of __call__ or refine, `measurer` a measure.BodyMeasurer on the same GPU.  Measures
         out['reposed_vertices'] -- the predicted shape in the T-pose -- with the T-pose joints as anchor points: one extra SMPL forward on
-        out['shape'] with identity rotations (its vertices are the reposed vertices again and are dropped).  `out` is not changed.
+        out['shape'] with identity rotations (its vertices are the reposed vertices again and are dropped).  posed=True: measures
+        out['vertices'], the body as posed, with out['joints'] as anchor points instead (no SMPL forward) -- for specs whose planes follow the
+        body (measure.posed_measurements(): `toward=`); planes with a fixed normal mean little there.  `out` is not changed.
         -> {'values': [B,M] float32, name: [B], ...} (BodyMeasurer.forward).  Never synchronises; capturable after a warm-up call."""
+        if posed:
+            with torch.no_grad():
+                return measurer(out['vertices'], out['joints'])
         with torch.no_grad():
             shape = out['shape'].contiguous()
             B = shape.shape[0]
