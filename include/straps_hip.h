@@ -1146,6 +1146,55 @@ int straps_fit_adam(const straps_fit_opts_t* opts, float* est /*[B][157] in/out*
         float* exp_avg, float* exp_avg_sq, float* energy, long long ld_energy, long long col, float* grad,
         float* best_est, float* best_energy, int step, int first, int update, long long batch, void* stream);
 
+/* ---- one body shape per subject across frames (csrc/fit_subjects.hip; added without a version change) ----------------------------
+ * straps_fit_adam_subjects: straps_fit_adam with the ten shape coefficients tied across the frames of a subject -- the update step of
+ * a fit loop in which several frames show one person.  The arguments it shares with straps_fit_adam mean what they mean there.
+ *
+ * Subjects and masks.  offsets [G + 1] int32 in DEVICE memory, non-decreasing (the caller's duty; the kernel only clamps): subject s
+ *   owns the contiguous rows lo .. hi - 1 with lo = clamp(offsets[s], 0, B), hi = clamp(offsets[s + 1], lo, B).  Rows that no subject
+ *   owns are not touched.  frame_mask [B] bytes or NULL: a frame whose byte is 0 does not COUNT towards its subject (NULL: all count).
+ * Per frame f (masked frames included): E_f, the gradient columns 0..146 (cam and pose), their moments in exp_avg / exp_avg_sq and
+ *   their update are exactly straps_fit_adam's, bit for bit; energy[f * ld_energy + col] = E_f.
+ * Shape, per subject: g_s[i] = the sum over the subject's counting frames of t_f[i], where t_f[i] is what straps_fit_adam forms for
+ *   column 147 + i (g_kp[f][147 + i] + dbetas[f][i], nothing added for a NULL), and E_s = the sum of the counting frames' E_f;
+ *   subject_energy[s * ld_subject + col] = E_s.  Both are fp32 sums in a fixed order: frame j of the subject belongs to partial j % 16,
+ *   a partial adds its counting frames in frame order, the partials are added in the order 0..15.  Only real terms are summed (a
+ *   partial starts from its first term, not from +0: a -0 stays a -0), so the order depends on the subject's frame count and mask
+ *   alone -- not on B, the subject's position or other subjects.  The current shape is read from the subject's FIRST row of est
+ *   (precondition: all rows of a subject hold the same shape columns).  With update != 0 the shape gets one Adam step from g_s, the
+ *   moments shape_avg[s] / shape_avg_sq[s] [G][10], lr_shape and t = step + 1, by the formula of straps_fit_adam; the ten new values
+ *   are written into EVERY row of the subject, masked ones included.  The shape columns of exp_avg / exp_avg_sq are neither read nor
+ *   written.  grad [B][157], when given: per-frame values in columns 0..146, g_s in columns 147..156 of every row of the subject.
+ * Best iterate, per subject: with first != 0, or when E_s < best_energy[s] (the first minimum wins, a NaN never replaces what is
+ *   held), all the subject's best_est rows receive the est rows as they were before the update, and best_energy[s] [G] = E_s.
+ * Edge cases.  update == 0 leaves est and all moments bit-identical.  A subject without a counting frame has E_s = 0 and g_s = 0,
+ *   and its shape and shape moments are left as they are, bit for bit (its frames' cam and pose are updated as ever).  An empty
+ *   subject (lo == hi) writes subject_energy 0 and nothing else.
+ * Consequence: if every subject has one frame and shape_avg / shape_avg_sq equal the shape columns of exp_avg / exp_avg_sq, then est,
+ *   energy, best_est, best_energy, grad and the cam / pose moments equal straps_fit_adam's bit for bit, and the shape moments equal
+ *   that call's shape-column moments.
+ * Arguments: as straps_fit_adam, and offsets must not be NULL, 1 <= n_subjects <= batch, update needs shape_avg and shape_avg_sq,
+ *   ld_subject >= 1 and 0 <= col < ld_subject when subject_energy is given.
+ *
+ * straps_subject_mean_rows: out[s][c] = the sum, in the same fixed order, of rows[f * ld + c] over the subject's counting rows,
+ *   divided by their number (fp32); with no counting row the plain mean over all rows of the subject; zeros for an empty subject.
+ *   1 <= cols <= 64, ld >= cols.
+ *
+ * Both check their arguments before any HIP call, launch one kernel on `stream` (one workgroup per subject; subjects of hundreds of
+ * frames are fine), use no workspace, allocate nothing, never synchronise, use no float atomics, are capturable and bit-reproducible;
+ * a subject's result depends on nothing but that subject's inputs.                                                                  */
+int straps_fit_adam_subjects(const straps_fit_opts_t* opts, float* est /*[B][157] in/out*/,
+        const int32_t* offsets /*DEVICE [G+1]*/, const uint8_t* frame_mask /*[B] or NULL = all count*/,
+        const float* g_kp, const float* dcam, const float* dx6, const float* dbetas,
+        const float* e_kp, const float* energy2, float w_in, float w_out,
+        float* exp_avg, float* exp_avg_sq /*[B][157]*/, float* shape_avg, float* shape_avg_sq /*[G][10]*/,
+        float* energy /*[B][ld_energy] per frame, or NULL*/, long long ld_energy, long long col,
+        float* subject_energy /*[G][ld_subject] or NULL*/, long long ld_subject,
+        float* grad /*[B][157] or NULL*/, float* best_est /*[B][157]*/, float* best_energy /*[G]*/,
+        int step, int first, int update, long long batch, long long n_subjects, void* stream);
+int straps_subject_mean_rows(const float* rows, long long ld, int cols /*1..64*/, const int32_t* offsets,
+        const uint8_t* frame_mask, float* out /*[G][cols]*/, long long batch, long long n_subjects, void* stream);
+
 /* ---- shaded picture of a mesh under the weak-perspective camera (csrc/render.hip; added without a version change) -----------------
  * What predict/predict_3D.py:169-178 draws through renderers/weak_perspective_pyrender_renderer.py, for a batch, on the device.  The
  * shading model is Lambert with an ambient term, NOT pyrender's metallic-roughness material: which face a pixel shows is defined

@@ -14,6 +14,9 @@ straps_fit_adam: csrc/silfit.hip): the projected vertices are pulled inside the 
 foreground pixels pull their nearest projected vertex towards them.  That term needs the whole mesh, so its loop is a sequence of entry
 points per iteration (SMPL forward and backward included), not one launch.  Its default weights (100 on both silhouette terms, lattice 4,
 tau 1.5 px) are those of a float64 prototype on the synthetic model as well: untuned on real detections.
+
+`SubjectFitter` is that loop for several frames of one person: cam and pose per frame, ONE shape per subject (straps_fit_adam_subjects and
+straps_subject_mean_rows, csrc/fit_subjects.hip, in the place of straps_fit_adam).
 """
 import ctypes as C
 
@@ -346,4 +349,164 @@ class SilhouetteFitter(KeypointFitter):
                'state': {'exp_avg': m, 'exp_avg_sq': v, 'step': step0 + self.iters}}
         if trace:
             out['trace'] = energy
+        return out
+
+
+def fit_adam_subjects_raw(opts, est, offsets, frame_mask, g_kp, dcam, dx6, dbetas, e_kp, energy2, w_in, w_out, exp_avg, exp_avg_sq, shape_avg, shape_avg_sq,
+                          energy, col, subject_energy, grad, best_est, best_energy, step, first, update, n_subjects):
+    """one straps_fit_adam_subjects call on contiguous GPU tensors (None -> NULL): offsets int32 [G+1], frame_mask uint8 [B]; energy [B,ld] and
+    subject_energy [G,ld'] receive column `col`"""
+    hipabi.check(hipabi.lib().straps_fit_adam_subjects(
+        C.byref(opts), hipabi.ptr(est), hipabi.ptr(offsets), hipabi.ptr(frame_mask), hipabi.ptr(g_kp), hipabi.ptr(dcam), hipabi.ptr(dx6), hipabi.ptr(dbetas),
+        hipabi.ptr(e_kp), hipabi.ptr(energy2), w_in, w_out, hipabi.ptr(exp_avg), hipabi.ptr(exp_avg_sq), hipabi.ptr(shape_avg), hipabi.ptr(shape_avg_sq),
+        hipabi.ptr(energy), 0 if energy is None else energy.shape[1], col, hipabi.ptr(subject_energy), 0 if subject_energy is None else subject_energy.shape[1],
+        hipabi.ptr(grad), hipabi.ptr(best_est), hipabi.ptr(best_energy), int(step), int(bool(first)), int(bool(update)), est.shape[0], int(n_subjects),
+        hipabi.stream_ptr()), 'straps_fit_adam_subjects')
+
+
+def subject_mean_rows_raw(rows, ld, cols, offsets, frame_mask, out, batch, n_subjects):
+    """one straps_subject_mean_rows call; rows: a tensor or a raw device address (a column block of a wider matrix), ld its row stride in floats"""
+    rp = C.c_void_p(rows) if isinstance(rows, int) else hipabi.ptr(rows)
+    hipabi.check(hipabi.lib().straps_subject_mean_rows(rp, ld, cols, hipabi.ptr(offsets), hipabi.ptr(frame_mask), hipabi.ptr(out), batch, n_subjects,
+                                                       hipabi.stream_ptr()), 'straps_subject_mean_rows')
+
+
+class SubjectFitter(SilhouetteFitter):
+    """`SubjectFitter(smpl)(cam, pose6d, shape, frames_per_subject, silhouettes, joints2D)`: SilhouetteFitter's objective with ONE shape per
+    subject.  The frames of a subject are consecutive rows; cam and pose stay per frame, the ten shape coefficients are shared: their gradient
+    is the sum over the subject's frames, their Adam step is one per subject (straps_fit_adam_subjects, csrc/fit_subjects.hip).  Without
+    silhouettes the keypoints and the priors alone are fitted (two launches per iteration).  What this buys is ONE shape that explains all the
+    frames as well as per-frame shapes do; on the synthetic model neither recovers the true coefficients.  Untuned on real data."""
+
+    def __init__(self, *a, **k):
+        SilhouetteFitter.__init__(self, *a, **k)
+        self._subjects = {}
+
+    def subjects(self, frames_per_subject, B, dev):
+        """host validation of the frame counts -> (G, offsets int32 [G+1], subject of every frame int64 [B], first row of every subject int64 [G]),
+        device tensors uploaded once per value and device"""
+        try:
+            fps = tuple(int(n) for n in frames_per_subject)
+            ok = len(fps) >= 1 and all(n >= 1 for n in fps) and all(n == m for n, m in zip(fps, frames_per_subject))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('SubjectFitter: frames_per_subject is a sequence of positive integers (got %r)' % (frames_per_subject,))
+        if sum(fps) != B:
+            raise ValueError('SubjectFitter: frames_per_subject sums to %d, the batch has %d frames' % (sum(fps), B))
+        key = (fps, str(dev))
+        if key not in self._subjects:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('SubjectFitter: the first call with a new frames_per_subject uploads its offsets: warm up before capturing')
+            off = np.concatenate([[0], np.cumsum(fps)]).astype(np.int32)
+            self._subjects[key] = (torch.from_numpy(off).to(dev), torch.from_numpy(np.repeat(np.arange(len(fps)), fps).astype(np.int64)).to(dev),
+                                   torch.from_numpy(off[:-1].astype(np.int64)).to(dev))
+        return (len(fps),) + self._subjects[key]
+
+    def _subject_inputs(self, cam, pose6d, shape, frames_per_subject, silhouettes, joints2D, conf, prior, frame_mask):
+        """-> est (shape tied to the subjects' means), est0, targets, conf, mask (None without silhouettes), frame mask, G, offsets, first rows"""
+        if silhouettes is None and joints2D is None:
+            raise ValueError('SubjectFitter: give silhouettes, joints2D or both')
+        hipabi.require_gpu_tensor(cam, 'cam', torch.float32)
+        B, dev = cam.shape[0], cam.device
+        G, offsets, subject_of, first_rows = self.subjects(frames_per_subject, B, dev)
+        if silhouettes is not None:
+            est, est0, targets, conf, mask = self._sil_inputs(cam, pose6d, shape, silhouettes, joints2D, conf, prior)
+        else:
+            est, est0, targets, conf = self._inputs(cam, pose6d, shape, joints2D, conf, prior)
+            mask = None
+            if est0 is None:
+                est0 = est.clone()      # (the prior centre stays per frame: the parameters as given, before the shapes are tied)
+        fm = None
+        if frame_mask is not None:
+            hipabi.require_gpu_tensor(frame_mask, 'frame_mask')
+            if tuple(frame_mask.shape) != (B,):
+                raise RuntimeError('SubjectFitter: frame_mask must be [%d], got %s' % (B, tuple(frame_mask.shape)))
+            fm = frame_mask.detach()
+            fm = fm.contiguous() if fm.dtype == torch.uint8 else (fm != 0).to(torch.uint8)
+        # the start: every subject's mean shape over its counting frames, in all its rows
+        mean = torch.empty(G, 10, device=dev, dtype=torch.float32)
+        subject_mean_rows_raw(est.data_ptr() + 147 * 4, NE, 10, offsets, fm, mean, B, G)
+        est[:, 147:] = mean.index_select(0, subject_of)
+        return est, est0, targets, conf, mask, fm, G, offsets, first_rows
+
+    def _subject_buffers(self, B, dev, mask):
+        if mask is not None:
+            return self._buffers(B, dev, mask)
+        f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
+        return {'e_kp': f(B, 1), 'g_kp': f(B, NE), 'kp2d': f(B, self.n_kp, 2), 'dcam': None, 'dx6': None, 'dbetas': None, 'energy2': None}
+
+    def _subject_terms(self, est, est0, targets, conf, mask, buf):
+        if mask is not None:
+            self._terms(est, est0, targets, conf, mask, buf)
+        else:      # (iters = 0 leaves est as it is, bit for bit)
+            fit_keypoints_raw(self._struct, self.opts(0), est, est0, targets, conf, None, None, buf['e_kp'], buf['g_kp'], None, None, buf['kp2d'])
+
+    @hipabi.on_tensor_device
+    def evaluate(self, cam, pose6d, shape, frames_per_subject, silhouettes=None, joints2D=None, conf=None, prior=None, frame_mask=None):
+        """-> (subject energy [G], grad [B,157] with the subject's summed shape gradient in columns 147..156 of all its rows, energy per frame [B])
+        at the given cam and pose and the subjects' mean shapes"""
+        est, est0, targets, conf, mask, fm, G, offsets, _ = self._subject_inputs(cam, pose6d, shape, frames_per_subject, silhouettes, joints2D, conf, prior,
+                                                                                frame_mask)
+        B, dev = est.shape[0], est.device
+        buf = self._subject_buffers(B, dev, mask)
+        self._subject_terms(est, est0, targets, conf, mask, buf)
+        energy = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        sub = torch.empty(G, 1, device=dev, dtype=torch.float32)
+        grad = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        fit_adam_subjects_raw(self.opts(), est, offsets, fm, buf['g_kp'], buf['dcam'], buf['dx6'], buf['dbetas'], buf['e_kp'], buf['energy2'], self.w_in,
+                              self.w_out, None, None, None, None, energy, 0, sub, grad, None, None, 0, True, False, G)
+        return sub[:, 0], grad, energy[:, 0]
+
+    @hipabi.on_tensor_device
+    def __call__(self, cam, pose6d, shape, frames_per_subject, silhouettes=None, joints2D=None, conf=None, prior=None, frame_mask=None, state=None,
+                 trace=False):
+        """cam [B,3], pose6d [B,144], shape [B,10]; frames_per_subject: positive ints summing to B (a host sequence: subject s owns the next
+        frames_per_subject[s] rows); silhouettes [B,img_wh,img_wh] and / or joints2D as for SilhouetteFitter (at least one); prior: the centre
+        of the priors, per frame (None = the parameters as given, so the tied shape is pulled towards every frame's own start); frame_mask [B]
+        (bool / uint8) or None: a frame whose entry is 0 neither pulls its subject's shape nor counts in its energy, and receives the shape;
+        state: the 'state' of an earlier call.  Every subject starts from the mean of its counting frames' shapes (straps_subject_mean_rows).
+        -> SilhouetteFitter's keys ('energy_terms' only with silhouettes; 'energy0' / 'energy' per frame [B]) plus 'subject_shape' [G,10],
+        'subject_energy0' / 'subject_energy' [G]; 'best' is chosen per subject by the subject's energy ('energy' [G]); 'state' also holds
+        'shape_avg' / 'shape_avg_sq' [G,10]; 'trace' [G,iters+1] (subject energies) if asked.  iters + 1 evaluations, iters updates, every
+        iteration SilhouetteFitter's six evaluating entry points (without silhouettes: straps_fit_keypoints with iters = 0) and
+        straps_fit_adam_subjects, on buffers allocated before the loop.  The inputs are not modified.  Never synchronises; after one warm-up
+        call with the same frames_per_subject and shapes it can be captured in torch.cuda.graph."""
+        est, est0, targets, conf, mask, fm, G, offsets, first_rows = self._subject_inputs(cam, pose6d, shape, frames_per_subject, silhouettes, joints2D, conf,
+                                                                                         prior, frame_mask)
+        B, dev = est.shape[0], est.device
+        if state is None:
+            m, v, step0 = torch.zeros(B, NE, device=dev), torch.zeros(B, NE, device=dev), 0
+            sm, sv = torch.zeros(G, 10, device=dev), torch.zeros(G, 10, device=dev)
+        else:
+            for k, want in (('exp_avg', (B, NE)), ('exp_avg_sq', (B, NE)), ('shape_avg', (G, 10)), ('shape_avg_sq', (G, 10))):
+                if k not in state:
+                    raise RuntimeError("SubjectFitter: state has no '%s' (the state of a per-frame fitter cannot be carried over)" % k)
+                hipabi.require_gpu_tensor(state[k], "state['%s']" % k, torch.float32)
+                if tuple(state[k].shape) != want:
+                    raise RuntimeError("SubjectFitter: state['%s'] must be %s, got %s" % (k, list(want), tuple(state[k].shape)))
+            m, v, sm, sv = (state[k].detach().clone(memory_format=torch.contiguous_format) for k in ('exp_avg', 'exp_avg_sq', 'shape_avg', 'shape_avg_sq'))
+            step0 = int(state['step'])
+        buf = self._subject_buffers(B, dev, mask)
+        energy = torch.empty(B, self.iters + 1, device=dev, dtype=torch.float32)
+        sub = torch.empty(G, self.iters + 1, device=dev, dtype=torch.float32)
+        best = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        best_e = torch.empty(G, device=dev, dtype=torch.float32)
+        opts = self.opts()
+        for i in range(self.iters + 1):
+            self._subject_terms(est, est0, targets, conf, mask, buf)
+            fit_adam_subjects_raw(opts, est, offsets, fm, buf['g_kp'], buf['dcam'], buf['dx6'], buf['dbetas'], buf['e_kp'], buf['energy2'], self.w_in, self.w_out,
+                                  m, v, sm, sv, energy, i, sub, None, best, best_e, step0 + i, i == 0, i < self.iters, G)
+        pose = est[:, 3:147]
+        out = {'cam_wp': est[:, :3], 'pose': pose, 'shape': est[:, 147:],
+               'pose_rotmats': buf['R'] if mask is not None else rot6d_to_rotmat(pose).view(B, 24, 3, 3),
+               'energy0': energy[:, 0], 'energy': energy[:, self.iters],
+               'subject_shape': est[:, 147:].index_select(0, first_rows), 'subject_energy0': sub[:, 0], 'subject_energy': sub[:, self.iters],
+               'best': {'cam_wp': best[:, :3], 'pose': best[:, 3:147], 'shape': best[:, 147:], 'energy': best_e},
+               'joints2D': cam_utils.undo_keypoint_normalisation(buf['kp2d'], self.img_wh),
+               'state': {'exp_avg': m, 'exp_avg_sq': v, 'shape_avg': sm, 'shape_avg_sq': sv, 'step': step0 + self.iters}}
+        if mask is not None:
+            out['energy_terms'] = torch.cat([buf['e_kp'], buf['energy2']], dim=1)
+        if trace:
+            out['trace'] = sub
         return out

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import cam_utils, config, hipabi
-from .fit import SilhouetteFitter
+from .fit import SilhouetteFitter, SubjectFitter
 from .infer import InferenceRegressor
 
 _PATCHES = {}
@@ -127,12 +127,16 @@ class Predictor:
                 'vertices2D': v2d, 'reposed_vertices': reposed, 'joints2D_cropped': jc, 'boxes': boxes, 'valid': boxes[:, 4] != 0}
 
     @hipabi.on_tensor_device
-    def refine(self, out, fitter, conf=None):
+    def refine(self, out, fitter, conf=None, subjects=None):
         """test-time fitting after the regressor: the parameters of `out` (a result of __call__) are fitted to out['joints2D_cropped'] by
         `fitter` (a fit.KeypointFitter, or a fit.SilhouetteFitter -- then also to the silhouette the regressor was given, out['proxy_rep'][:, 0] != 0,
         with 'energy_terms' [B,3] among the results -- on this SMPL module, with as many keypoints as joints2D had; its img_wh must be this predictor's
         out_wh: ValueError otherwise), with the regressor's answer as the centre of the priors.  conf [B,J] or None (all ones).  An invalid sample keeps its
         parameters bit for bit: its confidences are zeroed.
+        subjects: for a fit.SubjectFitter (ValueError without it, and with it for any other fitter) the frames_per_subject list -- positive ints
+        summing to B, subject s is the next subjects[s] frames: one shape per subject.  An invalid sample is passed as frame_mask = 0: it neither pulls
+        its subject's shape nor counts in its energy, keeps its cam and pose bit for bit and receives its subject's shape.  The result then also has
+        'subject_shape' [G,10], 'subject_energy0' / 'subject_energy' [G] and 'subjects' (the list).
         -> a dict with the keys of __call__, rebuilt from the fitted parameters by the same tail, plus the fitter's 'energy0' and 'energy'
         [B].  Never synchronises; capturable after a warm-up call."""
         with torch.no_grad():
@@ -143,16 +147,24 @@ class Predictor:
                                  'and has %d joints' % (fitter.img_wh, fitter.n_kp, self.out_wh, jc.shape[1]))
             conf = torch.ones(B, jc.shape[1], device=jc.device, dtype=torch.float32) if conf is None else conf.float()
             conf = conf * valid[:, None].to(conf.dtype)
+            if isinstance(fitter, SubjectFitter) != (subjects is not None):
+                raise ValueError('Predictor.refine: subjects= is required for a SubjectFitter and taken by no other fitter')
             if isinstance(fitter, SilhouetteFitter):
                 # the silhouette the regressor was given is the target; an invalid sample's mask is emptied: with zero confidences every gradient is zero
                 target = (out['proxy_rep'][:, 0] != 0) & valid[:, None, None].to(torch.bool)
-                fit = fitter(out['cam_wp'].contiguous(), out['pose'].contiguous(), out['shape'].contiguous(), target, jc, conf=conf)
+                if subjects is not None:      # (a SubjectFitter: an invalid sample does not count towards its subject's shape either)
+                    fit = fitter(out['cam_wp'].contiguous(), out['pose'].contiguous(), out['shape'].contiguous(), subjects, target, jc, conf=conf, frame_mask=valid)
+                else:
+                    fit = fitter(out['cam_wp'].contiguous(), out['pose'].contiguous(), out['shape'].contiguous(), target, jc, conf=conf)
             else:
                 fit = fitter(out['cam_wp'].contiguous(), out['pose'].contiguous(), out['shape'].contiguous(), jc, conf=conf)
             res = self._tail(out['proxy_rep'], fit['cam_wp'], fit['pose'], fit['shape'], fit['pose_rotmats'], jc, out['boxes'], None)
         res['energy0'], res['energy'] = fit['energy0'], fit['energy']
         if 'energy_terms' in fit:
             res['energy_terms'] = fit['energy_terms']
+        if subjects is not None:
+            res['subject_shape'], res['subject_energy0'], res['subject_energy'] = fit['subject_shape'], fit['subject_energy0'], fit['subject_energy']
+            res['subjects'] = [int(n) for n in subjects]
         return res
 
     @hipabi.on_tensor_device
@@ -192,3 +204,16 @@ class Predictor:
             B = shape.shape[0]
             _, joints = self.smpl.forward_arrays(shape, self._identity_rotmats(B, shape.device))
             return measurer(out['reposed_vertices'], joints)
+
+    @hipabi.on_tensor_device
+    def measure_subjects(self, out, measurer):
+        """body measurements per SUBJECT: `out` a result of refine(..., subjects=...), `measurer` a measure.BodyMeasurer on the same GPU.  Measures the
+        T-pose of out['subject_shape'] with the T-pose joints as anchor points -- `measure`'s non-posed route on G bodies: one SMPL forward with identity
+        rotations.  -> {'values': [G,M] float32, name: [G], ...}.  Never synchronises; capturable after a warm-up call."""
+        if 'subject_shape' not in out:
+            raise ValueError("Predictor.measure_subjects: `out` has no 'subject_shape': refine it with a SubjectFitter and subjects= first")
+        with torch.no_grad():
+            shape = out['subject_shape'].contiguous()
+            G = shape.shape[0]
+            verts, joints = self.smpl.forward_arrays(shape, self._identity_rotmats(G, shape.device))
+            return measurer(verts, joints)
