@@ -1244,7 +1244,7 @@ int straps_render_mesh(const float* verts, const int32_t* faces, const int32_t* 
 /* ---- body measurements of a batch of meshes (csrc/measure.hip; added without a version change) -------------------------------------
  * Volume, surface area, extent along a direction, planar girths and lengths along anchor points, n_meas of them per body, in one call.
  * Vertices and points are read as fp32; every product, sum, division and square root is done in double; each result is rounded to float
- * once.  out [B][n_meas].  Not differentiable.  A GIRTH is the length of the plane section, and planes and directions are the same for
+ * once.  out [B][n_meas].  Gradients: straps_measure_mesh_bwd below.  A GIRTH is the length of the plane section, and planes and directions are the same for
  * every body of the batch; tape-measure (convex hull) girths and per-body plane normals: straps_measure_tape below.
  *   anchor       a names vertex a of the body when 0 <= a < nverts, points[b][a - nverts] when nverts <= a < nverts + n_points
  *                (points [B][n_points][3], may be NULL when n_points == 0); -1 means "none".
@@ -1344,6 +1344,62 @@ size_t straps_measure_tape_workspace_bytes(long long batch, int nfaces, int n_me
 int straps_measure_tape(const float* verts, const float* points, const int32_t* faces, const uint8_t* face_parts,
         const straps_tape_t* meas, float* out, int32_t* counts, void* workspace, long long batch, int nverts, int n_points,
         int nfaces, int n_meas, int capacity, void* stream);
+
+/* ---- gradients of the body measurements and the energy head of a fit to known measurements (csrc/measure_bwd.hip; added without a
+ * version change) ------------------------------------------------------------------------------------------------------------------
+ * straps_measure_mesh_bwd: given dout [B][n_meas], the gradient of sum_m dout[b][m] * value_m of straps_measure_mesh w.r.t. the vertices,
+ *   dverts [B][nverts][3], and w.r.t. the anchor points, dpoints [B][dpoints_rows][3].  Tape girths (straps_measure_tape) have no gradient.
+ *   Anchors, selected faces, limits and argument checks are exactly straps_measure_mesh's.  In addition: dout and dverts must not be NULL;
+ *   vf_offsets / vf_faces -- the CSR vertex-to-face table of straps_render_mesh above (faces ascending, a face that names a vertex twice
+ *   listed once for it, out-of-range faces not listed) -- are required when any measurement reads faces; dpoints_rows >= n_points; dpoints
+ *   is required when any anchor that is read is a point (it may be NULL otherwise).  Every failure is STRAPS_EINVAL before any HIP call
+ *   and names the argument.
+ *   definition   the derivative of the exact-arithmetic function on the branch the forward took at these fp32 inputs: the same side tests
+ *                d_i >= 0, the same lone vertex, the same selected faces.  Per selected face and measurement:
+ *     VOLUME     d/dq_0 = (q_1 x q_2) / 6, cyclic over the corners; the centre c = anchor[0] receives minus the sum of the three.
+ *     AREA       with n = (p1 - p0) x (p2 - p0): d/dp_0 = (n / |n|) x (p2 - p1) / 2, cyclic.  A face with |n|^2 == 0 adds nothing.
+ *     GIRTH      the derivative of |x - x'| through t = d_a / (d_a - d_b) w.r.t. the three corners and the anchor o, which enters every
+ *                d_i.  A face that is not cut, or whose section length is exactly 0, adds nothing.
+ *     EXTENT     +dir * dout to the lowest-index vertex whose dir . p equals the maximum, -dir * dout to the lowest-index vertex that
+ *                equals the minimum (one vertex may be both).  A NaN maximum or minimum equals no vertex: nothing is added for it.
+ *     PATH       unit segment vectors to the anchors: +(A_j - A_(j-1)) / |.| and -(A_(j+1) - A_j) / |.| at position j, for every position
+ *                that names the anchor.  A zero-length segment adds nothing.
+ *     A face that names vertex v in several corners adds every one of those corners' gradients to v.  An anchor that is a vertex adds
+ *     into that vertex's dverts row; several measurements may share an anchor.
+ *   arithmetic   double throughout; each output element is rounded to float once, after all its terms -- anchor terms included -- are
+ *                added.  Order of the terms of dverts[b][v]: the incident faces in table order, per face the measurements in index order
+ *                (per measurement the corners 0, 1, 2 that name v); then the measurements in index order once more for what v receives
+ *                as an anchor or an extreme -- the anchor gradient of a GIRTH or centred VOLUME is the sum over blocks of 512 faces in
+ *                block order, each block a fixed tree.  dpoints[b][j]: the measurements in index order.  The order depends on the
+ *                topology and the measurement list alone: never on the batch size, the body's position in it, or timing.
+ *   outputs      dverts is written whole (+0 for a vertex without a term).  Rows 0 .. n_points - 1 of every body's dpoints are written
+ *                whole; rows n_points .. dpoints_rows - 1 are not touched -- a zeroed [B][90][3] buffer can go on to straps_smpl_bwd as
+ *                djoints.  dout == 0 is multiplied like any other value (0 * NaN is NaN).
+ *   workspace (8-byte aligned): straps_measure_bwd_workspace_bytes
+ *       = batch * n_meas * 8 * (3 * ceil(nfaces / 512) + 4 * ceil(nverts / 2048)) bytes, 0 for an argument outside the limits.
+ *   Two launches on `stream`.  Blocks of 512 faces (only for a GIRTH or centred VOLUME) and 2048 vertices (only for an EXTENT) of ONE body
+ *   write the anchor-gradient partials and (max, min, their lowest indices) in double; then one thread per (body, vertex) gathers: it
+ *   walks the vertex's incident faces, loads each face's corners once (four faces in flight) and adds the terms of all measurements, then
+ *   its anchor and extreme terms, and stores three floats; one more workgroup per body finishes the points, a thread per row.
+ * straps_measure_residual: the energy head of a shape fit to known measurements, one thread per body, fp32, in this order:
+ *   per column m = 0 .. n_meas - 1:  w = weights[b][m] (1 when weights is NULL); the column is KNOWN iff the target t is finite and non-zero
+ *     and w is finite and > 0.  Known: r = values / t - 1; wr = w * r; e = fmaf(wr, r, e) (e starts at +0); dvalues[b][m] = (2 wr) / t.
+ *     Unknown: the value is not read into any result (a NaN there is harmless) and dvalues[b][m] = +0.
+ *   prior:  d_i = est[b][147 + i] - est0[b][147 + i], p = fmaf(d_i, d_i, p) for i = 0 .. 9 (p starts at +0);
+ *     energy[b] = fmaf(lambda_shape, p, e);  g[b][147 + i] = (2 lambda_shape) * d_i;  g[b][0 .. 146] = +0.
+ *   values, targets, dvalues [B][n_meas]; est, est0, g [B][157]; energy [B]; 1 <= n_meas <= 32; lambda_shape >= 0.  energy and g are what
+ *   straps_fit_adam takes as e_kp and g_kp.  One launch.
+ * Both use no floating-point atomics, no allocation and no synchronisation, read nothing that the call has not written, are capturable
+ * and bit-reproducible; a body's rows are the same bits alone or in any batch, and a NaN body leaves the others untouched.            */
+size_t straps_measure_bwd_workspace_bytes(long long batch, int nverts, int nfaces, int n_meas);
+int straps_measure_mesh_bwd(const float* verts, const float* points, const int32_t* faces, const uint8_t* face_parts,
+        const int32_t* vf_offsets, const int32_t* vf_faces, const straps_measure_t* meas,
+        const float* dout /*[B][n_meas]*/, float* dverts /*[B][nverts][3]*/,
+        float* dpoints /*[B][dpoints_rows][3] or NULL*/, void* workspace,
+        long long batch, int nverts, int n_points, int dpoints_rows, int nfaces, int n_meas, void* stream);
+int straps_measure_residual(const float* values, const float* targets, const float* weights /*or NULL*/,
+        const float* est, const float* est0, float lambda_shape, float* energy, float* dvalues, float* g,
+        long long batch, int n_meas, void* stream);
 
 #ifdef __cplusplus
 }

@@ -580,3 +580,22 @@ class _SmplAaFn(torch.autograd.Function):
 
 def smpl_aa_forward_autograd(smpl, betas, full_pose_aa):
     return _SmplAaFn.apply(smpl, betas, full_pose_aa)
+
+
+class _MeasureFn(torch.autograd.Function):
+    """body measurements with a gradient: forward = straps_measure_mesh (BodyMeasurer.measure_arrays, the values of the no-grad path bit for
+    bit); backward = straps_measure_mesh_bwd (BodyMeasurer.measure_grad)."""
+
+    @staticmethod
+    def forward(ctx, measurer, vertices, joints):
+        ctx.measurer, ctx.v, ctx.j = measurer, vertices.detach(), None if joints is None else joints.detach()
+        return measurer.measure_arrays(vertices, joints)
+
+    @staticmethod
+    def backward(ctx, dvalues):
+        dverts, djoints = ctx.measurer.measure_grad(ctx.v, ctx.j, dvalues.contiguous())
+        return None, dverts, djoints
+
+
+def measure_autograd(measurer, vertices, joints=None):
+    return _MeasureFn.apply(measurer, vertices, joints)

@@ -510,3 +510,152 @@ class SubjectFitter(SilhouetteFitter):
         if trace:
             out['trace'] = sub
         return out
+
+
+SHAPE0 = 147      # first shape column of a [B,157] estimate row
+
+
+class MeasurementFitter:
+    """`MeasurementFitter(smpl, measurer)(shape, targets)`: the ten shape coefficients fitted to KNOWN body measurements -- a height, a chest
+    or waist girth -- of the T-pose body, by Adam on
+
+        E = sum_m w_m (value_m / target_m - 1)^2 + lambda_shape |beta - beta0|^2        (straps_measure_residual, include/straps_hip.h)
+
+    measurer: a measure.BodyMeasurer on the SMPL module's device without tape specs (tape girths have no gradient: ValueError).  targets
+    [B,M] in the order of measurer.names, NaN (or 0) = unknown; or a dict name -> float or [B] tensor, absent names unknown (a dict is
+    turned into a tensor by host code: pass a tensor to a call that is to be captured).  weights [B,M] or None (all ones); a weight that
+    is not > 0 makes the column unknown.  The residuals are relative, so a height in metres and a volume in cubic metres pull alike.
+    One iteration is SMPL forward with identity rotations, straps_measure_mesh, straps_measure_residual, straps_measure_mesh_bwd, straps_smpl_bwd
+    and straps_fit_adam on a [B,157] row whose cam and pose columns have zero gradient and come back as they went in.
+    The defaults (lr 0.05, 100 iterations, lambda 1e-3, relative residuals) are those of a float64 prototype on the synthetic model of this
+    package: untuned on a real SMPL model.  On the synthetic model, whose faces are a triangle soup, the fit lowers the energy but cannot be
+    expected to recover the coefficients."""
+
+    def __init__(self, smpl, measurer, iters=100, lr=0.05, lambda_shape=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        if measurer.tape_columns:
+            raise ValueError('MeasurementFitter: the measurer has the tape specs %r: tape girths (straps_measure_tape) have no gradient' % (list(measurer.tape_names),))
+        hipabi.require_gpu_tensor(smpl._k_j_template, 'SMPL model buffers (call .to(device))')
+        hipabi.require_gpu_tensor(measurer.faces, 'BodyMeasurer buffers (call .to(device))', torch.int32)
+        if measurer.num_vertices != smpl.v_template.shape[0]:
+            raise ValueError('MeasurementFitter: the measurer was built for %d vertices, the SMPL model has %d (BodyMeasurer.from_smpl)'
+                             % (measurer.num_vertices, smpl.v_template.shape[0]))
+        if measurer.needs_joints > 90:
+            raise ValueError('MeasurementFitter: the measurer reads joint %d, the SMPL module gives 90' % (measurer.needs_joints - 1))
+        self.smpl, self.measurer, self.device = smpl, measurer, smpl._k_j_template.device
+        self.iters, self.lr, self.lambda_shape = int(iters), float(lr), float(lambda_shape)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        if self.iters < 0 or not self.lambda_shape >= 0:
+            raise ValueError('MeasurementFitter: iters and lambda_shape must not be negative')
+
+    def opts(self):
+        return hipabi.FitOptsStruct(self.iters, 0, self.lr, self.lr, self.lr, self.betas[0], self.betas[1], self.eps, 0.0, 0.0, self.lambda_shape, 0.0)
+
+    def targets_tensor(self, targets, B, dev):
+        """targets [B,M] or a dict by measurement name -> float32 [B,M], NaN where unknown"""
+        M = len(self.measurer.names)
+        if isinstance(targets, dict):
+            unknown = [n for n in targets if n not in self.measurer.names]
+            if unknown:
+                raise ValueError('MeasurementFitter: the measurer has no measurement %r (it has %r)' % (unknown, list(self.measurer.names)))
+            t = torch.full((B, M), float('nan'), device=dev, dtype=torch.float32)
+            for n, v in targets.items():
+                t[:, self.measurer.names.index(n)] = v.detach().to(dev, torch.float32) if isinstance(v, torch.Tensor) else float(v)
+            return t
+        hipabi.require_gpu_tensor(targets, 'targets', torch.float32)
+        if tuple(targets.shape) != (B, M):
+            raise RuntimeError('MeasurementFitter: targets must be [%d,%d], got %s' % (B, M, tuple(targets.shape)))
+        return targets.detach().contiguous()
+
+    def _inputs(self, shape, targets, weights, prior):
+        hipabi.require_gpu_tensor(shape, 'shape', torch.float32)
+        if shape.dim() != 2 or shape.shape[1] != 10 or shape.shape[0] < 1:
+            raise RuntimeError('MeasurementFitter: shape must be [B,10], got %s' % (tuple(shape.shape),))
+        B, dev = shape.shape[0], shape.device
+        est = torch.zeros(B, NE, device=dev, dtype=torch.float32)
+        est[:, SHAPE0:] = shape.detach()
+        est0 = est.clone()
+        if prior is not None:
+            hipabi.require_gpu_tensor(prior, 'prior', torch.float32)
+            if tuple(prior.shape) != (B, 10):
+                raise RuntimeError('MeasurementFitter: prior must be [%d,10], got %s' % (B, tuple(prior.shape)))
+            est0[:, SHAPE0:] = prior.detach()
+        targets = self.targets_tensor(targets, B, dev)
+        if weights is not None:
+            hipabi.require_gpu_tensor(weights, 'weights', torch.float32)
+            if tuple(weights.shape) != tuple(targets.shape):
+                raise RuntimeError('MeasurementFitter: weights must be %s, got %s' % (list(targets.shape), tuple(weights.shape)))
+            weights = weights.detach().contiguous()
+        return est, est0, targets, weights
+
+    def _buffers(self, B, dev):
+        L, ms = hipabi.lib(), self.measurer
+        V, F, M, P = self.smpl.v_template.shape[0], ms.faces.shape[0], len(ms.names), ms.needs_joints
+        f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
+        return {'R': torch.eye(3, device=dev, dtype=torch.float32).expand(B, 24, 3, 3).contiguous(), 'betas': f(B, 10), 'verts': f(B, V, 3), 'joints': f(B, 90, 3),
+                'points': f(B, P, 3) if P else None, 'values': f(B, M), 'dvalues': f(B, M), 'e': f(B), 'g': f(B, NE), 'dverts': f(B, V, 3),
+                'djoints': torch.zeros(B, 90, 3, device=dev, dtype=torch.float32) if P else None, 'dbetas': f(B, 10), 'drot': f(B, 24, 3, 3),
+                'ws': torch.empty(L.straps_measure_workspace_bytes(B, V, F, M) // 8, device=dev, dtype=torch.float64),
+                'ws_grad': torch.empty(L.straps_measure_bwd_workspace_bytes(B, V, F, M) // 8, device=dev, dtype=torch.float64),
+                'ws_bwd': f(L.straps_smpl_bwd_workspace_bytes(B, 0) // 4)}
+
+    def _terms(self, est, est0, targets, weights, buf):
+        """the five evaluating entry points of one iteration at `est` (steps 1 to 5 of the loop); the results are left in `buf`"""
+        L, st, B, ms = hipabi.lib(), hipabi.stream_ptr(), est.shape[0], self.measurer
+        buf['betas'].copy_(est[:, SHAPE0:])
+        self.smpl.forward_arrays(buf['betas'], buf['R'], out_verts=buf['verts'], out_joints=buf['joints'])
+        if buf['points'] is not None:
+            buf['points'].copy_(buf['joints'][:, :ms.needs_joints])
+        ms.measure_raw(buf['verts'], buf['points'], buf['values'], buf['ws'])
+        hipabi.check(L.straps_measure_residual(hipabi.ptr(buf['values']), hipabi.ptr(targets), hipabi.ptr(weights), hipabi.ptr(est), hipabi.ptr(est0),
+                                               self.lambda_shape, hipabi.ptr(buf['e']), hipabi.ptr(buf['dvalues']), hipabi.ptr(buf['g']), B, targets.shape[1], st),
+                     'straps_measure_residual')
+        ms.measure_grad_raw(buf['verts'], buf['points'], buf['dvalues'], buf['dverts'], buf['djoints'], buf['ws_grad'])
+        hipabi.check(L.straps_smpl_bwd(C.byref(self.smpl._model_struct()), hipabi.ptr(buf['betas']), hipabi.ptr(buf['R']), hipabi.ptr(buf['dverts']),
+                                       hipabi.ptr(buf['djoints']), hipabi.ptr(buf['dbetas']), hipabi.ptr(buf['drot']), hipabi.ptr(buf['ws_bwd']), B, 0, st),
+                     'straps_smpl_bwd')
+
+    @hipabi.on_tensor_device
+    def evaluate(self, shape, targets, weights=None, prior=None):
+        """-> (energy [B], grad [B,10], values [B,M]) at the given shape"""
+        est, est0, targets, weights = self._inputs(shape, targets, weights, prior)
+        B, dev = est.shape[0], est.device
+        buf = self._buffers(B, dev)
+        self._terms(est, est0, targets, weights, buf)
+        energy = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        grad = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        fit_adam_raw(self.opts(), est, buf['g'], None, None, buf['dbetas'], buf['e'], None, 0.0, 0.0, None, None, energy, 0, grad, None, None, 0, True, False)
+        return energy[:, 0], grad[:, SHAPE0:], buf['values']
+
+    @hipabi.on_tensor_device
+    def __call__(self, shape, targets, weights=None, prior=None, state=None, trace=False):
+        """shape [B,10] (the start), targets / weights as the class docstring says, prior [B,10]: the centre of the shape prior (None = the
+        start), state: the 'state' of an earlier call (the Adam moments and step count go on from there).
+        -> {'shape' [B,10], 'values' [B,M] (the measurements at the returned shape), 'energy0' [B], 'energy' [B] (at the returned shape),
+        'best': {'shape', 'energy'} (the iterate of the smallest energy), 'state', 'trace' [B,iters+1] if asked}.  iters + 1 evaluations,
+        iters updates, on buffers allocated before the loop.  The inputs are not modified.  Never synchronises; after one warm-up call at the
+        same shapes it can be captured in torch.cuda.graph."""
+        est, est0, targets, weights = self._inputs(shape, targets, weights, prior)
+        B, dev = est.shape[0], est.device
+        if state is None:
+            m, v, step0 = torch.zeros(B, NE, device=dev), torch.zeros(B, NE, device=dev), 0
+        else:
+            for k in ('exp_avg', 'exp_avg_sq'):
+                hipabi.require_gpu_tensor(state[k], "state['%s']" % k, torch.float32)
+                if tuple(state[k].shape) != (B, NE):
+                    raise RuntimeError("MeasurementFitter: state['%s'] must be [%d,157], got %s" % (k, B, tuple(state[k].shape)))
+            m, v = (state[k].detach().clone(memory_format=torch.contiguous_format) for k in ('exp_avg', 'exp_avg_sq'))
+            step0 = int(state['step'])
+        buf = self._buffers(B, dev)
+        energy = torch.empty(B, self.iters + 1, device=dev, dtype=torch.float32)
+        best = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        best_e = torch.empty(B, device=dev, dtype=torch.float32)
+        opts = self.opts()
+        for i in range(self.iters + 1):
+            self._terms(est, est0, targets, weights, buf)
+            fit_adam_raw(opts, est, buf['g'], None, None, buf['dbetas'], buf['e'], None, 0.0, 0.0, m, v, energy, i, None, best, best_e, step0 + i, i == 0,
+                         i < self.iters)
+        out = {'shape': est[:, SHAPE0:], 'values': buf['values'], 'energy0': energy[:, 0], 'energy': energy[:, self.iters],
+               'best': {'shape': best[:, SHAPE0:], 'energy': best_e}, 'state': {'exp_avg': m, 'exp_avg_sq': v, 'step': step0 + self.iters}}
+        if trace:
+            out['trace'] = energy
+        return out

@@ -20,7 +20,10 @@ helpers has either a `normal` shared by the batch or `toward`: a second anchor, 
 body -- a plane perpendicular to a bone, wherever the pose has put it.
 
 All arithmetic is double on fp32 vertices, rounded to float once; results are bit-reproducible and a body's row depends on that body alone.
-The calls are not differentiable.
+
+Gradients (csrc/measure_bwd.hip, straps_measure_mesh_bwd): `measurer(vertices, joints, differentiable=True)` gives the same values with a
+gradient to vertices and joints, `measurer.measure_grad(vertices, joints, dvalues)` the gradient itself; fit.MeasurementFitter fits the shape
+to known measurements with them.  The five kinds above only: tape girths (`tape_girth`, `section_girth`) have no gradient.
 """
 import collections
 import ctypes as C
@@ -228,9 +231,12 @@ class BodyMeasurer(nn.Module):
     measurements=None: default_measurements().  Specs of tape_girth / section_girth go to straps_measure_tape, the others to
     straps_measure_mesh (a call without specs of one sort is not made); `values` holds the columns in the order of `names`.  tape_capacity:
     the section points per (body, tape measurement) that the workspace holds, None: the worst case, 2 * faces.  A tape girth of a body
-    that cuts more is NaN; measure_counts tells how many there were."""
+    that cuts more is NaN; measure_counts tells how many there were.  num_vertices: the vertex count of the meshes that measure_grad will get,
+    for the vertex-to-face table of the gradient's gather (`vf_offsets` / `vf_faces`, nmr_renderer.vertex_face_table, built here once and moved
+    with the module);
+    None: the highest index in `faces` + 1, which is wrong only when the last vertices are in no face (from_smpl passes the model's count)."""
 
-    def __init__(self, faces=None, face_parts=None, measurements=None, tape_capacity=None):
+    def __init__(self, faces=None, face_parts=None, measurements=None, tape_capacity=None, num_vertices=None):
         super().__init__()
         name = 'BodyMeasurer'
         if faces is None:
@@ -280,15 +286,27 @@ class BodyMeasurer(nn.Module):
                                    % (name, 2 * faces.shape[0], tape_capacity))
             tape_capacity = int(tape_capacity)
         self.tape_capacity = tape_capacity
+        # the CSR vertex-to-face table of the gradient's gather (straps_measure_mesh_bwd), built once.  Derived from `faces`, so neither in the
+        # state dict nor among named_buffers(): plain tensors that _apply moves with the module
+        from .nmr_renderer import vertex_face_table
+        self.num_vertices = int(num_vertices) if num_vertices is not None else max(1, int(faces.max()) + 1 if faces.size else 1)
+        vf_offsets, vf_faces = vertex_face_table(faces, self.num_vertices)
+        self.vf_offsets, self.vf_faces = torch.from_numpy(vf_offsets), torch.from_numpy(vf_faces)
         self._structs = {}
         self._tape_structs = {}
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        self.vf_offsets, self.vf_faces = fn(self.vf_offsets), fn(self.vf_faces)
+        return self
 
     @classmethod
     def from_smpl(cls, smpl, measurements=None, tape_capacity=None):
         """the face and part tables of an SMPL module (its `.faces` / `.face_parts`: the model file's, or the synthetic model's)"""
         if getattr(smpl, 'faces', None) is None:
             raise RuntimeError('BodyMeasurer.from_smpl: the SMPL model carries no faces; pass faces= (and face_parts=) to BodyMeasurer')
-        return cls(smpl.faces, getattr(smpl, 'face_parts', None), measurements, tape_capacity)
+        nv = getattr(smpl, 'v_template', None)
+        return cls(smpl.faces, getattr(smpl, 'face_parts', None), measurements, tape_capacity, None if nv is None else nv.shape[0])
 
     @hipabi.on_tensor_device
     def measure_arrays(self, vertices, joints=None):
@@ -302,7 +320,8 @@ class BodyMeasurer(nn.Module):
         whatever tape_capacity is: a count above it is a NaN tape girth.  Runs the tape call alone; never synchronises."""
         return self._measure(vertices, joints, True)
 
-    def _measure(self, vertices, joints, want_counts):
+    def _checked_inputs(self, vertices, joints):
+        """the checks every call makes -> (vertices detached and contiguous, points [B,needs_joints,3] or None, B, N)"""
         name = 'BodyMeasurer'
         hipabi.require_gpu_tensor(vertices, 'vertices', torch.float32)
         hipabi.require_gpu_tensor(self.faces, name + ' buffers (call .to(device))', torch.int32)
@@ -322,7 +341,11 @@ class BodyMeasurer(nn.Module):
             for a in s.anchors:
                 if not isinstance(a, tuple) and a >= N:
                     raise RuntimeError('%s: measurement %r is anchored at vertex %d, the mesh has %d' % (name, n, a, N))
-        vertices = vertices.detach().contiguous()
+        return vertices.detach().contiguous(), points, B, N
+
+    def _measure(self, vertices, joints, want_counts):
+        name = 'BodyMeasurer'
+        vertices, points, B, N = self._checked_inputs(vertices, joints)
         L = hipabi.lib()
         F = self.faces.shape[0]
         # both calls get the SAME points tensor, [B, needs_joints, 3]: its row count is the stride by which they find a body's points, whatever the
@@ -363,9 +386,71 @@ class BodyMeasurer(nn.Module):
         src.update({i: tape_out[:, k] for k, i in enumerate(self.tape_columns)})
         return torch.stack([src[i] for i in range(len(self.specs))], 1)
 
-    def forward(self, vertices, joints=None):
-        """-> {'values': [B,M] float32, name: [B] (a view of its column), ...} in the order of `self.names`"""
-        values = self.measure_arrays(vertices, joints)
+    @hipabi.on_tensor_device
+    def measure_grad(self, vertices, joints, dvalues):
+        """the gradient of sum(dvalues * values) w.r.t. the inputs of measure_arrays (straps_measure_mesh_bwd; include/straps_hip.h defines it at
+        ties and degenerate terms): vertices [B,N,3], joints None or [B,J,3], dvalues [B,M] in the order of `names`
+        -> (dvertices [B,N,3], djoints [B,J,3] or None without joints; rows of joints that no spec reads are zero).  Tape girths have no
+        gradient: a non-zero dvalues column of a tape spec raises (that check reads the device, and is made only when there are tape specs).
+        Otherwise never synchronises; capturable."""
+        name = 'BodyMeasurer.measure_grad'
+        if not self.mesh_columns:
+            raise RuntimeError('%s: every measurement is a tape girth: straps_measure_tape has no gradient' % name)
+        vertices, points, B, N = self._checked_inputs(vertices, joints)
+        hipabi.require_gpu_tensor(dvalues, 'dvalues', torch.float32)
+        if tuple(dvalues.shape) != (B, len(self.specs)):
+            raise RuntimeError('%s: dvalues must be [%d,%d], got %s' % (name, B, len(self.specs), tuple(dvalues.shape)))
+        if N != self.num_vertices:
+            raise RuntimeError('%s: the vertex-to-face table was built for %d vertices, the mesh has %d (BodyMeasurer(..., num_vertices=))' % (name, self.num_vertices, N))
+        dvalues = dvalues.detach()
+        if self.tape_columns:
+            if bool((dvalues[:, list(self.tape_columns)] != 0).any()):
+                raise RuntimeError('%s: dvalues is non-zero in a column of %r: tape girths (straps_measure_tape) have no gradient' % (name, list(self.tape_names)))
+            dvalues = dvalues[:, list(self.mesh_columns)]
+        dvalues = dvalues.contiguous()
+        dverts = torch.empty(B, N, 3, device=vertices.device, dtype=torch.float32)
+        djoints = None if joints is None else torch.zeros(B, joints.shape[1], 3, device=vertices.device, dtype=torch.float32)
+        ws = torch.empty(hipabi.lib().straps_measure_bwd_workspace_bytes(B, N, self.faces.shape[0], len(self.mesh_columns)) // 8, device=vertices.device,
+                         dtype=torch.float64)
+        self.measure_grad_raw(vertices, points, dvalues, dverts, djoints, ws)
+        return dverts, djoints
+
+    def _mesh_structs(self, N):
+        """the straps_measure_t array of the non-tape specs for meshes of N vertices (joint anchors resolve to N + j), built once per N"""
+        if N not in self._structs:
+            self._structs[N] = measure_structs([self.specs[i] for i in self.mesh_columns], N)
+        return self._structs[N][0]
+
+    def measure_raw(self, vertices, points, out, workspace):
+        """one straps_measure_mesh call for the non-tape specs on contiguous GPU tensors: points None or [B,needs_joints,3], out
+        [B,len(mesh_columns)]; what measure_arrays launches, on the caller's buffers"""
+        B, N, F = vertices.shape[0], vertices.shape[1], self.faces.shape[0]
+        hipabi.check(hipabi.lib().straps_measure_mesh(hipabi.ptr(vertices), hipabi.ptr(points), hipabi.ptr(self.faces) if F else None, hipabi.ptr(self.face_parts),
+                                                      self._mesh_structs(N), hipabi.ptr(out), hipabi.ptr(workspace), B, N, self.needs_joints, F, len(self.mesh_columns),
+                                                      hipabi.stream_ptr()), 'straps_measure_mesh')
+
+    def measure_grad_raw(self, vertices, points, dvalues, dverts, dpoints, workspace):
+        """one straps_measure_mesh_bwd call for the non-tape specs on contiguous GPU tensors: points None or [B,needs_joints,3], dvalues
+        [B,len(mesh_columns)], dpoints None or [B,rows >= needs_joints,3] (rows the specs do not read are left as they are)"""
+        B, N, F = vertices.shape[0], vertices.shape[1], self.faces.shape[0]
+        hipabi.check(hipabi.lib().straps_measure_mesh_bwd(
+            hipabi.ptr(vertices), hipabi.ptr(points), hipabi.ptr(self.faces) if F else None, hipabi.ptr(self.face_parts), hipabi.ptr(self.vf_offsets),
+            hipabi.ptr(self.vf_faces) if self.vf_faces.numel() else None, self._mesh_structs(N), hipabi.ptr(dvalues), hipabi.ptr(dverts), hipabi.ptr(dpoints),
+            hipabi.ptr(workspace), B, N, self.needs_joints, 0 if dpoints is None else dpoints.shape[1], F, len(self.mesh_columns), hipabi.stream_ptr()),
+            'straps_measure_mesh_bwd')
+
+    def forward(self, vertices, joints=None, differentiable=False):
+        """-> {'values': [B,M] float32, name: [B] (a view of its column), ...} in the order of `self.names`.  differentiable=True: the values
+        carry a gradient to `vertices` and `joints` (autograd_ops.measure_autograd: straps_measure_mesh forward, straps_measure_mesh_bwd
+        backward); a measurer with tape specs raises, tape girths have none.  The default computes exactly what it always did."""
+        if differentiable:
+            if self.tape_columns:
+                raise RuntimeError('BodyMeasurer: differentiable=True with the tape specs %r: tape girths (straps_measure_tape) have no gradient'
+                                   % (list(self.tape_names),))
+            from .autograd_ops import measure_autograd
+            values = measure_autograd(self, vertices, joints)
+        else:
+            values = self.measure_arrays(vertices, joints)
         res = {'values': values}
         for i, n in enumerate(self.names):
             res[n] = values[:, i]

@@ -168,6 +168,25 @@ class Predictor:
         return res
 
     @hipabi.on_tensor_device
+    def refine_shape(self, out, mfitter, targets, weights=None):
+        """the predicted shape made to agree with KNOWN measurements of the subject (a height, a girth): `out` a result of __call__ or refine,
+        `mfitter` a fit.MeasurementFitter on this SMPL module, targets / weights as MeasurementFitter.__call__ takes them ([B,M] tensors in the
+        order of the measurer's names, NaN = unknown; targets may be a dict by name).  The fit starts from out['shape'] and uses it as the
+        centre of the shape prior; cam and pose stay as they are.  An invalid sample gets all-zero weights and keeps its shape bit for bit.
+        -> a dict with the keys of __call__, rebuilt from the fitted shape by the same tail, plus the fitter's 'energy0' and 'energy' [B] and
+        'measurements' [B,M]: the values at the fitted shape.  Never synchronises (with tensor targets); capturable after a warm-up call."""
+        with torch.no_grad():
+            shape, valid = out['shape'].contiguous(), out['valid']
+            B = shape.shape[0]
+            targets = mfitter.targets_tensor(targets, B, shape.device)
+            w = torch.ones_like(targets) if weights is None else weights.float()
+            w = w * valid[:, None].to(w.dtype)
+            fit = mfitter(shape, targets, weights=w.contiguous())
+            res = self._tail(out['proxy_rep'], out['cam_wp'], out['pose'], fit['shape'], out['pose_rotmats'], out['joints2D_cropped'], out['boxes'], None)
+        res['energy0'], res['energy'], res['measurements'] = fit['energy0'], fit['energy'], fit['values']
+        return res
+
+    @hipabi.on_tensor_device
     def render(self, out, renderer, images=None):
         """predict_3D.py:170-174 for the batch: `out` a result of __call__ or refine, `renderer` a nmr_renderer.WeakPerspectiveMeshRenderer on the
         same GPU, images None or uint8 [B,wh,wh,3] on the GPU (the pictures the predictions are drawn over; wh must be renderer.img_wh:
