@@ -1332,7 +1332,8 @@ int straps_measure_mesh(const float* verts, const float* points, const int32_t* 
  * on coordinates alone, to the lexicographic maximum; the same way back -- and adds the edge lengths in chain order.  Every step moves
  * strictly forward in lexicographic order, so a chain ends after at most `count` steps whatever rounding does to an orientation test.
  * No allocation, no synchronisation, no floating-point atomics, nothing read that the call has not written; capturable;
- * bit-reproducible; a row depends on that body's inputs alone (same bits alone or in a batch; a NaN body leaves the others untouched). */
+ * bit-reproducible; a row depends on that body's inputs alone (same bits alone or in a batch; a NaN body leaves the others untouched).
+ * Gradients: straps_measure_tape_bwd below. */
 enum { STRAPS_TAPE_HULL = 0, STRAPS_TAPE_SECTION = 1 };
 typedef struct {
     int32_t kind;
@@ -1348,7 +1349,7 @@ int straps_measure_tape(const float* verts, const float* points, const int32_t* 
 /* ---- gradients of the body measurements and the energy head of a fit to known measurements (csrc/measure_bwd.hip; added without a
  * version change) ------------------------------------------------------------------------------------------------------------------
  * straps_measure_mesh_bwd: given dout [B][n_meas], the gradient of sum_m dout[b][m] * value_m of straps_measure_mesh w.r.t. the vertices,
- *   dverts [B][nverts][3], and w.r.t. the anchor points, dpoints [B][dpoints_rows][3].  Tape girths (straps_measure_tape) have no gradient.
+ *   dverts [B][nverts][3], and w.r.t. the anchor points, dpoints [B][dpoints_rows][3].  Tape girths (straps_measure_tape): straps_measure_tape_bwd below.
  *   Anchors, selected faces, limits and argument checks are exactly straps_measure_mesh's.  In addition: dout and dverts must not be NULL;
  *   vf_offsets / vf_faces -- the CSR vertex-to-face table of straps_render_mesh above (faces ascending, a face that names a vertex twice
  *   listed once for it, out-of-range faces not listed) -- are required when any measurement reads faces; dpoints_rows >= n_points; dpoints
@@ -1400,6 +1401,68 @@ int straps_measure_mesh_bwd(const float* verts, const float* points, const int32
 int straps_measure_residual(const float* values, const float* targets, const float* weights /*or NULL*/,
         const float* est, const float* est0, float lambda_shape, float* energy, float* dvalues, float* g,
         long long batch, int n_meas, void* stream);
+
+/* ---- gradients of the tape-measure girths (csrc/measure_tape_bwd.hip; added without a version change) ----------------------------------
+ * straps_measure_tape_bwd: given dout [B][n_meas], the gradient of sum_m dout[b][m] * value_m of straps_measure_tape w.r.t. the vertices,
+ *   dverts [B][nverts][3], and w.r.t. the anchor points, dpoints [B][dpoints_rows][3].  `meas`, `capacity`, anchors, selected faces, limits
+ *   and argument checks are exactly straps_measure_tape's (without `out`).  In addition: dout and dverts must not be NULL; vf_offsets /
+ *   vf_faces -- the CSR vertex-to-face table of straps_render_mesh, as for straps_measure_mesh_bwd -- are required; dpoints_rows >= n_points;
+ *   dpoints is required when anchor[0] or anchor[1] of any measurement is a point (it may be NULL otherwise); accumulate is 0 or 1.
+ *   Every failure is STRAPS_EINVAL before any HIP call and names the argument.
+ *   definition   the derivative of the exact-arithmetic function on the branch the forward took at these fp32 inputs: the same side tests
+ *                d_i >= 0, the same lone vertex, the same selected faces, the same chain of hull corners.
+ *     section point   x = p_a + t (p_b - p_a), t = d_a / (d_a - d_b), d_i = n . (p_i - o).  With g the upstream gradient w.r.t. x,
+ *                e = p_b - p_a, D = n . e (= d_b - d_a) and s = (g . e) / D:
+ *                    dp_a += (1 - t)(g - s n)     dp_b += t (g - s n)     do += s n     dn += -s (x - o)
+ *                With a per-body normal (anchor[1] != -1: n = A1 - A0, o = A0): dA1 += dn and dA0 += do - dn.  With a fixed dir, dn is
+ *                dropped: there is no gradient w.r.t. dir.
+ *     SECTION    a cut face adds |x - x'|: g = +(x - x') / |x - x'| at x and the opposite at x'.  A face whose length is exactly 0 adds
+ *                nothing (GIRTH's rule).
+ *     HULL       the perimeter is sum_i |h_(i+1) - h_i| over the corners the march took, cyclic, in chain order: the lower chain from the
+ *                lexicographic minimum, then the upper chain.  Corner i receives (h_i - h_(i-1)) / |.| + (h_i - h_(i+1)) / |.|, taken in
+ *                the plane's basis: g = g_u u + g_v v.  The basis (u, v) is a constant: the perimeter does not depend on it.  Two corners
+ *                (a collinear set) give twice the unit vector, by the same formula; no point, or one distinct point, gives nothing.  The
+ *                march knows a corner by its coordinates: among the stored section points whose (u, v) equal the corner's (bit for bit,
+ *                but -0 equals +0), the one with the LOWEST slot index receives the gradient -- slot order is face order, as in the
+ *                forward, point 2 s of slot s on the edge (a, b), point 2 s + 1 on (a, c).
+ *     special rows    Unlike straps_measure_mesh_bwd, a (body, measurement) row with dout == +-0 adds NOTHING and is not marched: a fit has
+ *                unknown columns, and a NaN value there stays harmless.  A HULL row that is NaN in the forward (a non-finite section point,
+ *                or a count above `capacity`) puts, with a non-zero dout, NaN into the three components of the gradient row of its
+ *                anchor[0] and adds nothing else.  A normal that cuts nothing (zero, or non-finite) adds nothing.
+ *   arithmetic   double throughout; each output element is rounded to float once, after all its terms -- anchor terms included -- are
+ *                added.  Order of the terms of dverts[b][v]: the incident faces in table order, per face the measurements in index order,
+ *                per measurement the corners 0, 1, 2 that name v, per corner point 0 (the edge (a, b)) then point 1; then the measurements
+ *                in index order once more for what v receives as anchor[0] (do - dn, or do), then as anchor[1] (dn).  do and dn of a row are
+ *                sums over its cut faces: a SECTION's per thread over the trips of 256 faces in face order, a HULL's per thread over the
+ *                slots s = t, t + 256, .. in slot order; then the 64 lanes of a wave in a fixed tree, then the four waves in order.
+ *                dpoints[b][j]: the measurements in index order.  The order depends on the topology, the measurement list and that body's
+ *                own chain alone: never on the batch size, the body's position in it, or timing.
+ *   outputs      accumulate == 0: dverts is written whole (+0 for a vertex without a term); rows 0 .. n_points - 1 of every body's dpoints
+ *                are written whole; rows n_points .. dpoints_rows - 1 are not touched.  accumulate == 1: an element becomes
+ *                (float)((double)old + sum) -- the tape terms go onto straps_measure_mesh_bwd's output without another pass.
+ *   values, counts   [B][n_meas] or NULL: what straps_measure_tape writes to `out` and `counts` at the same arguments, BIT FOR BIT -- how a
+ *                caller sees that the same branch was taken.  The call is self-contained: it reads no forward call's workspace.
+ *   workspace (8-byte aligned), with cap = capacity, or 2 * nfaces when capacity == 0:
+ *       straps_measure_tape_bwd_workspace_bytes = batch * n_meas * 8 * (10 + 4 * cap + ceil(ceil(cap / 2) / 2)) bytes
+ *   -- per (body, measurement) ten doubles (count, section length, status, do, dn, one spare), cap (u, v) pairs, cap (g_u, g_v) pairs and
+ *   ceil(cap / 2) int32 face indices of the cut slots, padded to a double -- and 0 for an argument outside the limits (nverts included)
+ *   or a size of 2^62 bytes or more.  The kernels touch only the slots they fill.
+ *   Three launches on `stream` (two without a HULL).  collect: the forward's collect kernel, statement for statement, which also stores
+ *   the face index of every cut slot and adds a SECTION's do and dn.  hull: the forward's march with candidates that carry their index
+ *   (among equal coordinates the lower index wins); it writes (g_u, g_v) per stored point, zero for a point that is no corner, and adds a
+ *   HULL's do and dn over the slots whose points hold a vector.  gather: one thread per (body, vertex) walks the vertex's incident faces
+ *   (four in flight), per HULL finds the face's slot by binary search in the row's ascending face-index list, recomputes t, e, D and adds
+ *   its terms, then its anchor terms, and stores three floats; one more workgroup per body finishes the points, a thread per row.
+ *   No allocation, no synchronisation, no floating-point atomics, nothing read that the call has not written (with accumulate == 1:
+ *   besides dverts and dpoints); capturable; bit-reproducible; a body's rows are the same bits alone or in any batch, and a NaN body
+ *   leaves the others untouched.                                                                                                      */
+size_t straps_measure_tape_bwd_workspace_bytes(long long batch, int nverts, int nfaces, int n_meas, int capacity);
+int straps_measure_tape_bwd(const float* verts, const float* points, const int32_t* faces, const uint8_t* face_parts,
+        const int32_t* vf_offsets, const int32_t* vf_faces, const straps_tape_t* meas,
+        const float* dout /*[B][n_meas]*/, float* dverts /*[B][nverts][3]*/,
+        float* dpoints /*[B][dpoints_rows][3] or NULL*/, float* values /*[B][n_meas] or NULL*/, int32_t* counts /*or NULL*/,
+        void* workspace, long long batch, int nverts, int n_points, int dpoints_rows, int nfaces, int n_meas, int capacity,
+        int accumulate, void* stream);
 
 #ifdef __cplusplus
 }

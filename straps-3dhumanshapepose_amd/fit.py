@@ -521,19 +521,23 @@ class MeasurementFitter:
 
         E = sum_m w_m (value_m / target_m - 1)^2 + lambda_shape |beta - beta0|^2        (straps_measure_residual, include/straps_hip.h)
 
-    measurer: a measure.BodyMeasurer on the SMPL module's device without tape specs (tape girths have no gradient: ValueError).  targets
+    measurer: a measure.BodyMeasurer on the SMPL module's device; with tape specs (tape_girth / section_girth: what a tape reads) only one
+    made with tape_gradients=True (ValueError otherwise: without it a measurer does not differentiate tape girths).  targets
     [B,M] in the order of measurer.names, NaN (or 0) = unknown; or a dict name -> float or [B] tensor, absent names unknown (a dict is
     turned into a tensor by host code: pass a tensor to a call that is to be captured).  weights [B,M] or None (all ones); a weight that
     is not > 0 makes the column unknown.  The residuals are relative, so a height in metres and a volume in cubic metres pull alike.
     One iteration is SMPL forward with identity rotations, straps_measure_mesh, straps_measure_residual, straps_measure_mesh_bwd, straps_smpl_bwd
-    and straps_fit_adam on a [B,157] row whose cam and pose columns have zero gradient and come back as they went in.
+    and straps_fit_adam on a [B,157] row whose cam and pose columns have zero gradient and come back as they went in.  With tape specs an
+    iteration also runs straps_measure_tape (before the residual) and straps_measure_tape_bwd with accumulate = 1 (onto
+    straps_measure_mesh_bwd's output); a call without specs of one sort is not made.
     The defaults (lr 0.05, 100 iterations, lambda 1e-3, relative residuals) are those of a float64 prototype on the synthetic model of this
     package: untuned on a real SMPL model.  On the synthetic model, whose faces are a triangle soup, the fit lowers the energy but cannot be
     expected to recover the coefficients."""
 
     def __init__(self, smpl, measurer, iters=100, lr=0.05, lambda_shape=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        if measurer.tape_columns:
-            raise ValueError('MeasurementFitter: the measurer has the tape specs %r: tape girths (straps_measure_tape) have no gradient' % (list(measurer.tape_names),))
+        if measurer.tape_columns and not getattr(measurer, 'tape_gradients', False):
+            raise ValueError('MeasurementFitter: the measurer has the tape specs %r: tape girths (straps_measure_tape) have no gradient without '
+                             'BodyMeasurer(..., tape_gradients=True)' % (list(measurer.tape_names),))
         hipabi.require_gpu_tensor(smpl._k_j_template, 'SMPL model buffers (call .to(device))')
         hipabi.require_gpu_tensor(measurer.faces, 'BodyMeasurer buffers (call .to(device))', torch.int32)
         if measurer.num_vertices != smpl.v_template.shape[0]:
@@ -546,6 +550,10 @@ class MeasurementFitter:
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         if self.iters < 0 or not self.lambda_shape >= 0:
             raise ValueError('MeasurementFitter: iters and lambda_shape must not be negative')
+        # with tape specs: the columns of `values` that each library call fills, as device indices (uploaded here, so that a call can be captured)
+        self._columns = None
+        if measurer.tape_columns:
+            self._columns = tuple(torch.tensor(c, dtype=torch.int64).to(self.device) for c in (list(measurer.mesh_columns), list(measurer.tape_columns)))
 
     def opts(self):
         return hipabi.FitOptsStruct(self.iters, 0, self.lr, self.lr, self.lr, self.betas[0], self.betas[1], self.eps, 0.0, 0.0, self.lambda_shape, 0.0)
@@ -590,26 +598,49 @@ class MeasurementFitter:
     def _buffers(self, B, dev):
         L, ms = hipabi.lib(), self.measurer
         V, F, M, P = self.smpl.v_template.shape[0], ms.faces.shape[0], len(ms.names), ms.needs_joints
+        Mm, T = len(ms.mesh_columns), len(ms.tape_columns)
         f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
-        return {'R': torch.eye(3, device=dev, dtype=torch.float32).expand(B, 24, 3, 3).contiguous(), 'betas': f(B, 10), 'verts': f(B, V, 3), 'joints': f(B, 90, 3),
-                'points': f(B, P, 3) if P else None, 'values': f(B, M), 'dvalues': f(B, M), 'e': f(B), 'g': f(B, NE), 'dverts': f(B, V, 3),
-                'djoints': torch.zeros(B, 90, 3, device=dev, dtype=torch.float32) if P else None, 'dbetas': f(B, 10), 'drot': f(B, 24, 3, 3),
-                'ws': torch.empty(L.straps_measure_workspace_bytes(B, V, F, M) // 8, device=dev, dtype=torch.float64),
-                'ws_grad': torch.empty(L.straps_measure_bwd_workspace_bytes(B, V, F, M) // 8, device=dev, dtype=torch.float64),
-                'ws_bwd': f(L.straps_smpl_bwd_workspace_bytes(B, 0) // 4)}
+        buf = {'R': torch.eye(3, device=dev, dtype=torch.float32).expand(B, 24, 3, 3).contiguous(), 'betas': f(B, 10), 'verts': f(B, V, 3), 'joints': f(B, 90, 3),
+               'points': f(B, P, 3) if P else None, 'values': f(B, M), 'dvalues': f(B, M), 'e': f(B), 'g': f(B, NE), 'dverts': f(B, V, 3),
+               'djoints': torch.zeros(B, 90, 3, device=dev, dtype=torch.float32) if P else None, 'dbetas': f(B, 10), 'drot': f(B, 24, 3, 3),
+               'ws': torch.empty(L.straps_measure_workspace_bytes(B, V, F, Mm) // 8, device=dev, dtype=torch.float64),
+               'ws_grad': torch.empty(L.straps_measure_bwd_workspace_bytes(B, V, F, Mm) // 8, device=dev, dtype=torch.float64),
+               'ws_bwd': f(L.straps_smpl_bwd_workspace_bytes(B, 0) // 4)}
+        if T:      # the two calls' own columns, gathered into / scattered from `values` / `dvalues` in the order of measurer.names
+            buf.update({'mesh_values': f(B, Mm), 'mesh_dvalues': f(B, Mm), 'tape_values': f(B, T), 'tape_dvalues': f(B, T),
+                        'ws_tape': torch.empty(ms.tape_workspace_bytes(B) // 8, device=dev, dtype=torch.float64),
+                        'ws_tape_grad': torch.empty(ms.tape_grad_workspace_bytes(B, V) // 8, device=dev, dtype=torch.float64)})
+        return buf
 
     def _terms(self, est, est0, targets, weights, buf):
-        """the five evaluating entry points of one iteration at `est` (steps 1 to 5 of the loop); the results are left in `buf`"""
+        """the five evaluating entry points of one iteration at `est` (steps 1 to 5 of the loop; seven with tape specs); the results are left in `buf`"""
         L, st, B, ms = hipabi.lib(), hipabi.stream_ptr(), est.shape[0], self.measurer
         buf['betas'].copy_(est[:, SHAPE0:])
         self.smpl.forward_arrays(buf['betas'], buf['R'], out_verts=buf['verts'], out_joints=buf['joints'])
         if buf['points'] is not None:
             buf['points'].copy_(buf['joints'][:, :ms.needs_joints])
-        ms.measure_raw(buf['verts'], buf['points'], buf['values'], buf['ws'])
+        tape = bool(ms.tape_columns)
+        if not tape:
+            ms.measure_raw(buf['verts'], buf['points'], buf['values'], buf['ws'])
+        else:
+            mesh_idx, tape_idx = self._columns
+            if ms.mesh_columns:
+                ms.measure_raw(buf['verts'], buf['points'], buf['mesh_values'], buf['ws'])
+                buf['values'].index_copy_(1, mesh_idx, buf['mesh_values'])
+            ms.measure_tape_raw(buf['verts'], buf['points'], buf['tape_values'], buf['ws_tape'])
+            buf['values'].index_copy_(1, tape_idx, buf['tape_values'])
         hipabi.check(L.straps_measure_residual(hipabi.ptr(buf['values']), hipabi.ptr(targets), hipabi.ptr(weights), hipabi.ptr(est), hipabi.ptr(est0),
                                                self.lambda_shape, hipabi.ptr(buf['e']), hipabi.ptr(buf['dvalues']), hipabi.ptr(buf['g']), B, targets.shape[1], st),
                      'straps_measure_residual')
-        ms.measure_grad_raw(buf['verts'], buf['points'], buf['dvalues'], buf['dverts'], buf['djoints'], buf['ws_grad'])
+        if not tape:
+            ms.measure_grad_raw(buf['verts'], buf['points'], buf['dvalues'], buf['dverts'], buf['djoints'], buf['ws_grad'])
+        else:
+            if ms.mesh_columns:
+                torch.index_select(buf['dvalues'], 1, mesh_idx, out=buf['mesh_dvalues'])
+                ms.measure_grad_raw(buf['verts'], buf['points'], buf['mesh_dvalues'], buf['dverts'], buf['djoints'], buf['ws_grad'])
+            torch.index_select(buf['dvalues'], 1, tape_idx, out=buf['tape_dvalues'])
+            ms.measure_tape_grad_raw(buf['verts'], buf['points'], buf['tape_dvalues'], buf['dverts'], buf['djoints'], buf['ws_tape_grad'],
+                                     accumulate=bool(ms.mesh_columns))
         hipabi.check(L.straps_smpl_bwd(C.byref(self.smpl._model_struct()), hipabi.ptr(buf['betas']), hipabi.ptr(buf['R']), hipabi.ptr(buf['dverts']),
                                        hipabi.ptr(buf['djoints']), hipabi.ptr(buf['dbetas']), hipabi.ptr(buf['drot']), hipabi.ptr(buf['ws_bwd']), B, 0, st),
                      'straps_smpl_bwd')

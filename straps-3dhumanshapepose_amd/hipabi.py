@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'conv_wgrad.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
-           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'fit_subjects.hip', 'render.hip', 'measure.hip', 'val.hip', 'measure_tape.hip', 'measure_bwd.hip']
+           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'fit_subjects.hip', 'render.hip', 'measure.hip', 'val.hip', 'measure_tape.hip', 'measure_bwd.hip', 'measure_tape_bwd.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -370,6 +370,9 @@ SIGNATURES = {
     'straps_measure_bwd_workspace_bytes': (_Z, [_L, _I, _I, _I]),
     'straps_measure_mesh_bwd': (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(MeasureStruct), _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
     'straps_measure_residual': (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _P, _L, _I, _P]),
+    # gradients of straps_measure_tape: tape girths and section lengths, per-body planes (csrc/measure_tape_bwd.hip; added without a version change)
+    'straps_measure_tape_bwd_workspace_bytes': (_Z, [_L, _I, _I, _I, _I]),
+    'straps_measure_tape_bwd': (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(TapeStruct), _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
     'straps_comm_unique_id': (_I, [_P]),
     'straps_comm_init_rank': (_I, [_P, _I, _I, C.POINTER(C.c_void_p)]),
     'straps_comm_destroy': (_I, [_P]),

@@ -23,7 +23,8 @@ All arithmetic is double on fp32 vertices, rounded to float once; results are bi
 
 Gradients (csrc/measure_bwd.hip, straps_measure_mesh_bwd): `measurer(vertices, joints, differentiable=True)` gives the same values with a
 gradient to vertices and joints, `measurer.measure_grad(vertices, joints, dvalues)` the gradient itself; fit.MeasurementFitter fits the shape
-to known measurements with them.  The five kinds above only: tape girths (`tape_girth`, `section_girth`) have no gradient.
+to known measurements with them.  Tape girths (`tape_girth`, `section_girth`) have one with `BodyMeasurer(..., tape_gradients=True)`
+(csrc/measure_tape_bwd.hip, straps_measure_tape_bwd); without it a measurer refuses to differentiate them, as it always did.
 """
 import collections
 import ctypes as C
@@ -234,9 +235,11 @@ class BodyMeasurer(nn.Module):
     that cuts more is NaN; measure_counts tells how many there were.  num_vertices: the vertex count of the meshes that measure_grad will get,
     for the vertex-to-face table of the gradient's gather (`vf_offsets` / `vf_faces`, nmr_renderer.vertex_face_table, built here once and moved
     with the module);
-    None: the highest index in `faces` + 1, which is wrong only when the last vertices are in no face (from_smpl passes the model's count)."""
+    None: the highest index in `faces` + 1, which is wrong only when the last vertices are in no face (from_smpl passes the model's count).
+    tape_gradients=True: measure_grad, forward(differentiable=True) and fit.MeasurementFitter also serve the tape specs
+    (straps_measure_tape_bwd); the default refuses them, as it always did."""
 
-    def __init__(self, faces=None, face_parts=None, measurements=None, tape_capacity=None, num_vertices=None):
+    def __init__(self, faces=None, face_parts=None, measurements=None, tape_capacity=None, num_vertices=None, tape_gradients=False):
         super().__init__()
         name = 'BodyMeasurer'
         if faces is None:
@@ -286,6 +289,7 @@ class BodyMeasurer(nn.Module):
                                    % (name, 2 * faces.shape[0], tape_capacity))
             tape_capacity = int(tape_capacity)
         self.tape_capacity = tape_capacity
+        self.tape_gradients = bool(tape_gradients)
         # the CSR vertex-to-face table of the gradient's gather (straps_measure_mesh_bwd), built once.  Derived from `faces`, so neither in the
         # state dict nor among named_buffers(): plain tensors that _apply moves with the module
         from .nmr_renderer import vertex_face_table
@@ -301,12 +305,12 @@ class BodyMeasurer(nn.Module):
         return self
 
     @classmethod
-    def from_smpl(cls, smpl, measurements=None, tape_capacity=None):
+    def from_smpl(cls, smpl, measurements=None, tape_capacity=None, tape_gradients=False):
         """the face and part tables of an SMPL module (its `.faces` / `.face_parts`: the model file's, or the synthetic model's)"""
         if getattr(smpl, 'faces', None) is None:
             raise RuntimeError('BodyMeasurer.from_smpl: the SMPL model carries no faces; pass faces= (and face_parts=) to BodyMeasurer')
         nv = getattr(smpl, 'v_template', None)
-        return cls(smpl.faces, getattr(smpl, 'face_parts', None), measurements, tape_capacity, None if nv is None else nv.shape[0])
+        return cls(smpl.faces, getattr(smpl, 'face_parts', None), measurements, tape_capacity, None if nv is None else nv.shape[0], tape_gradients)
 
     @hipabi.on_tensor_device
     def measure_arrays(self, vertices, joints=None):
@@ -390,12 +394,13 @@ class BodyMeasurer(nn.Module):
     def measure_grad(self, vertices, joints, dvalues):
         """the gradient of sum(dvalues * values) w.r.t. the inputs of measure_arrays (straps_measure_mesh_bwd; include/straps_hip.h defines it at
         ties and degenerate terms): vertices [B,N,3], joints None or [B,J,3], dvalues [B,M] in the order of `names`
-        -> (dvertices [B,N,3], djoints [B,J,3] or None without joints; rows of joints that no spec reads are zero).  Tape girths have no
-        gradient: a non-zero dvalues column of a tape spec raises (that check reads the device, and is made only when there are tape specs).
-        Otherwise never synchronises; capturable."""
+        -> (dvertices [B,N,3], djoints [B,J,3] or None without joints; rows of joints that no spec reads are zero).  Tape girths have a
+        gradient with tape_gradients=True (straps_measure_tape_bwd, added onto the other kinds' in the same buffers; a call without specs
+        of one sort is not made).  Without it a non-zero dvalues column of a tape spec raises (that check reads the device, and is made
+        only when there are tape specs).  Otherwise never synchronises; capturable."""
         name = 'BodyMeasurer.measure_grad'
-        if not self.mesh_columns:
-            raise RuntimeError('%s: every measurement is a tape girth: straps_measure_tape has no gradient' % name)
+        if not self.mesh_columns and not self.tape_gradients:
+            raise RuntimeError('%s: every measurement is a tape girth: straps_measure_tape has no gradient without tape_gradients=True' % name)
         vertices, points, B, N = self._checked_inputs(vertices, joints)
         hipabi.require_gpu_tensor(dvalues, 'dvalues', torch.float32)
         if tuple(dvalues.shape) != (B, len(self.specs)):
@@ -403,16 +408,24 @@ class BodyMeasurer(nn.Module):
         if N != self.num_vertices:
             raise RuntimeError('%s: the vertex-to-face table was built for %d vertices, the mesh has %d (BodyMeasurer(..., num_vertices=))' % (name, self.num_vertices, N))
         dvalues = dvalues.detach()
+        tape_dvalues = None
         if self.tape_columns:
-            if bool((dvalues[:, list(self.tape_columns)] != 0).any()):
-                raise RuntimeError('%s: dvalues is non-zero in a column of %r: tape girths (straps_measure_tape) have no gradient' % (name, list(self.tape_names)))
+            if self.tape_gradients:
+                tape_dvalues = dvalues[:, list(self.tape_columns)].contiguous()
+            elif bool((dvalues[:, list(self.tape_columns)] != 0).any()):
+                raise RuntimeError('%s: dvalues is non-zero in a column of %r: tape girths (straps_measure_tape) have no gradient without tape_gradients=True'
+                                   % (name, list(self.tape_names)))
             dvalues = dvalues[:, list(self.mesh_columns)]
         dvalues = dvalues.contiguous()
         dverts = torch.empty(B, N, 3, device=vertices.device, dtype=torch.float32)
         djoints = None if joints is None else torch.zeros(B, joints.shape[1], 3, device=vertices.device, dtype=torch.float32)
-        ws = torch.empty(hipabi.lib().straps_measure_bwd_workspace_bytes(B, N, self.faces.shape[0], len(self.mesh_columns)) // 8, device=vertices.device,
-                         dtype=torch.float64)
-        self.measure_grad_raw(vertices, points, dvalues, dverts, djoints, ws)
+        if self.mesh_columns:
+            ws = torch.empty(hipabi.lib().straps_measure_bwd_workspace_bytes(B, N, self.faces.shape[0], len(self.mesh_columns)) // 8, device=vertices.device,
+                             dtype=torch.float64)
+            self.measure_grad_raw(vertices, points, dvalues, dverts, djoints, ws)
+        if tape_dvalues is not None:
+            ws = torch.empty(self.tape_grad_workspace_bytes(B, N) // 8, device=vertices.device, dtype=torch.float64)
+            self.measure_tape_grad_raw(vertices, points, tape_dvalues, dverts, djoints, ws, accumulate=bool(self.mesh_columns))
         return dverts, djoints
 
     def _mesh_structs(self, N):
@@ -439,14 +452,53 @@ class BodyMeasurer(nn.Module):
             hipabi.ptr(workspace), B, N, self.needs_joints, 0 if dpoints is None else dpoints.shape[1], F, len(self.mesh_columns), hipabi.stream_ptr()),
             'straps_measure_mesh_bwd')
 
+    def _tape_structs_for(self, N):
+        """the straps_tape_t array of the tape specs for meshes of N vertices, built once per N"""
+        if N not in self._tape_structs:
+            self._tape_structs[N] = tape_structs([self.specs[i] for i in self.tape_columns], N)
+        return self._tape_structs[N][0]
+
+    def tape_workspace_bytes(self, B):
+        """bytes of the workspace of measure_tape_raw for a batch of B"""
+        return hipabi.lib().straps_measure_tape_workspace_bytes(B, self.faces.shape[0], len(self.tape_columns), self.tape_capacity or 0)
+
+    def tape_grad_workspace_bytes(self, B, N):
+        """bytes of the workspace of measure_tape_grad_raw for a batch of B meshes of N vertices"""
+        n = hipabi.lib().straps_measure_tape_bwd_workspace_bytes(B, N, self.faces.shape[0], len(self.tape_columns), self.tape_capacity or 0)
+        if not n:
+            raise RuntimeError('BodyMeasurer: no tape gradient workspace for batch %d, %d vertices, %d faces, %d tape measurements, capacity %d'
+                               % (B, N, self.faces.shape[0], len(self.tape_columns), self.tape_capacity or 0))
+        return n
+
+    def measure_tape_raw(self, vertices, points, out, workspace, counts=None):
+        """one straps_measure_tape call for the tape specs on contiguous GPU tensors: points None or [B,needs_joints,3], out
+        [B,len(tape_columns)], counts None or int32 of that shape; what measure_arrays launches, on the caller's buffers"""
+        B, N, F = vertices.shape[0], vertices.shape[1], self.faces.shape[0]
+        hipabi.check(hipabi.lib().straps_measure_tape(hipabi.ptr(vertices), hipabi.ptr(points), hipabi.ptr(self.faces), hipabi.ptr(self.face_parts),
+                                                      self._tape_structs_for(N), hipabi.ptr(out), hipabi.ptr(counts), hipabi.ptr(workspace), B, N, self.needs_joints, F,
+                                                      len(self.tape_columns), self.tape_capacity or 0, hipabi.stream_ptr()), 'straps_measure_tape')
+
+    def measure_tape_grad_raw(self, vertices, points, dvalues, dverts, dpoints, workspace, accumulate=False, values=None, counts=None):
+        """one straps_measure_tape_bwd call for the tape specs on contiguous GPU tensors: points None or [B,needs_joints,3], dvalues
+        [B,len(tape_columns)], dpoints None or [B,rows >= needs_joints,3] (rows the specs do not read are left as they are); accumulate: add
+        to what dverts / dpoints hold (straps_measure_mesh_bwd's output, say) instead of overwriting it; values / counts: None or
+        [B,len(tape_columns)] float32 / int32, filled with what straps_measure_tape gives"""
+        B, N, F = vertices.shape[0], vertices.shape[1], self.faces.shape[0]
+        hipabi.check(hipabi.lib().straps_measure_tape_bwd(
+            hipabi.ptr(vertices), hipabi.ptr(points), hipabi.ptr(self.faces), hipabi.ptr(self.face_parts), hipabi.ptr(self.vf_offsets), hipabi.ptr(self.vf_faces),
+            self._tape_structs_for(N), hipabi.ptr(dvalues), hipabi.ptr(dverts), hipabi.ptr(dpoints), hipabi.ptr(values), hipabi.ptr(counts), hipabi.ptr(workspace), B, N,
+            self.needs_joints, 0 if dpoints is None else dpoints.shape[1], F, len(self.tape_columns), self.tape_capacity or 0, 1 if accumulate else 0,
+            hipabi.stream_ptr()), 'straps_measure_tape_bwd')
+
     def forward(self, vertices, joints=None, differentiable=False):
         """-> {'values': [B,M] float32, name: [B] (a view of its column), ...} in the order of `self.names`.  differentiable=True: the values
         carry a gradient to `vertices` and `joints` (autograd_ops.measure_autograd: straps_measure_mesh forward, straps_measure_mesh_bwd
-        backward); a measurer with tape specs raises, tape girths have none.  The default computes exactly what it always did."""
+        backward); a measurer with tape specs raises unless it was made with tape_gradients=True (then straps_measure_tape_bwd serves
+        them).  The default computes exactly what it always did."""
         if differentiable:
-            if self.tape_columns:
-                raise RuntimeError('BodyMeasurer: differentiable=True with the tape specs %r: tape girths (straps_measure_tape) have no gradient'
-                                   % (list(self.tape_names),))
+            if self.tape_columns and not self.tape_gradients:
+                raise RuntimeError('BodyMeasurer: differentiable=True with the tape specs %r: tape girths (straps_measure_tape) have no gradient without '
+                                   'tape_gradients=True' % (list(self.tape_names),))
             from .autograd_ops import measure_autograd
             values = measure_autograd(self, vertices, joints)
         else:
