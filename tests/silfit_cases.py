@@ -2,8 +2,8 @@
 and their cases (tests/test_silfit_cases_cpu.py, tests/test_gpu_distance_field.py, tests/test_gpu_silhouette_energy.py,
 tests/test_gpu_fit_silhouette.py).
 
-The objective of include/straps_hip.h restated in float64: a brute-force distance transform (every pixel against every foreground pixel),
-the two energies in torch with autograd for the gradients, and the composed fit on the oracle alone -- `O.rot6d_to_rotmat`,
+The objective of include/straps_hip.h restated in float64: a brute-force distance transform (every pixel against every foreground pixel; a
+row-blocked two-pass transform, held equal to it on the CPU, stands in above 257 pixels), the two energies in torch with autograd for the gradients, and the composed fit on the oracle alone -- `O.rot6d_to_rotmat`,
 `O.smpl_forward(MODEL, ..., dtype=float64)`, `O.orthographic_project`, `fit_cases.energy` for the keypoint and prior terms, `torch.optim.Adam`
 with three parameter groups.  All inputs come from `detgen.det_uniform`.
 """
@@ -42,17 +42,24 @@ def brute_d2(mask):
     rr, cc = torch.meshgrid(torch.arange(wh, dtype=torch.int32), torch.arange(wh, dtype=torch.int32), indexing='ij')
     P = torch.stack([rr.reshape(-1), cc.reshape(-1)], dim=1)
     out = torch.empty(wh * wh, dtype=torch.int32)
-    step = max(1, (1 << 24) // fg.shape[0])
+    step = max(1, (1 << 21) // fg.shape[0])      # (8 MiB per temporary, in place: three times as fast as 64 MiB ones and `** 2`)
     for a in range(0, wh * wh, step):
         p = P[a:a + step]
-        d = (p[:, None, 0] - fg[None, :, 0]) ** 2 + (p[:, None, 1] - fg[None, :, 1]) ** 2
-        out[a:a + step] = d.min(dim=1).values
+        d = p[:, None, 0] - fg[None, :, 0]
+        d.mul_(d)
+        e = p[:, None, 1] - fg[None, :, 1]
+        e.mul_(e)
+        out[a:a + step] = d.add_(e).min(dim=1).values
     return out.view(wh, wh).numpy()
+
+
+ROW_BLOCK = 8      # rows per block of the row pass: [8, wh, wh] int32 is 32 MiB at wh = 1024 (all rows at once would be 4 GiB)
 
 
 def two_pass_d2(mask):
     """the same transform as a column pass (distance to the nearest foreground row of the column) and a row pass (min over c' of
-    (c - c')^2 + g(c')^2): the structure of csrc/silfit.hip, in integers"""
+    (c - c')^2 + g(c')^2): the structure of csrc/silfit.hip, in integers.  The row pass runs over blocks of ROW_BLOCK rows (a row's result
+    depends on that row of g alone, so the blocking changes nothing); every value stays below 3 * wh * wh <= 2^22, int32 holds it."""
     mask = np.asarray(mask) != 0
     wh = mask.shape[0]
     far = 2 * wh
@@ -65,11 +72,13 @@ def two_pass_d2(mask):
     for r in range(wh - 1, -1, -1):
         run = np.where(mask[r], 0, np.minimum(run + 1, far))
         g[r] = np.minimum(g[r], run)
-    g2 = np.where(g >= far, sentinel(wh), g * g)
-    c = np.arange(wh)
+    g2 = torch.from_numpy(np.where(g >= far, sentinel(wh), g * g).astype(np.int32))
+    c = torch.arange(wh, dtype=torch.int32)
     dc2 = (c[:, None] - c[None, :]) ** 2                                   # [c][c']
-    out = (dc2[None, :, :] + g2[:, None, :]).min(axis=2)
-    return np.minimum(out, sentinel(wh)).astype(np.int32)
+    out = torch.empty(wh, wh, dtype=torch.int32)
+    for r0 in range(0, wh, ROW_BLOCK):
+        out[r0:r0 + ROW_BLOCK] = (dc2[None, :, :] + g2[r0:r0 + ROW_BLOCK, None, :]).min(dim=2).values
+    return out.clamp_(max=sentinel(wh)).numpy()
 
 
 def mask_cases(wh):
@@ -97,14 +106,57 @@ def mask_batches(wh):
     return out
 
 
+SPARSE = ('corner_tl', 'corner_tr', 'corner_bl', 'corner_br', 'rand1e4')
+
+
+def sparse_mask_cases(wh):
+    """-> ordered {name: uint8 [wh,wh]} of the masks on which brute force stays affordable at wh = 1024: the four corner cases of mask_cases
+    and a random one at density 1e-4 (about a hundred foreground pixels at wh = 1000; pixel (wh // 2, wh // 3) is set, so it is never empty)"""
+    mc = mask_cases(wh)
+    out = {k: mc[k] for k in SPARSE[:4]}
+    m = (det_uniform((wh, wh), 5400 + wh, 0.0, 1.0) < 1e-4).astype(np.uint8) * 255
+    m[wh // 2, wh // 3] = 255
+    out['rand1e4'] = m
+    return out
+
+
+def _mask(wh, name):
+    return sparse_mask_cases(wh)[name] if name == 'rand1e4' else mask_cases(wh)[name]
+
+
 _D2 = {}
 
 
 def reference_d2(wh, name):
     """brute-force transform of a mask case, computed once per process"""
     if (wh, name) not in _D2:
-        _D2[(wh, name)] = brute_d2(mask_cases(wh)[name])
+        _D2[(wh, name)] = brute_d2(_mask(wh, name))
     return _D2[(wh, name)]
+
+
+_D2_TWO_PASS = {}
+
+
+def reference_d2_two_pass(wh, name):
+    """the row-blocked two-pass transform of a mask case, computed once per process: the reference above wh = 257, where brute force on a dense
+    mask is out of reach (tests/test_silfit_cases_cpu.py holds the two equal at every size up to 257 on all masks, and at 1000 and 1024 on the
+    sparse ones)"""
+    if (wh, name) not in _D2_TWO_PASS:
+        _D2_TWO_PASS[(wh, name)] = two_pass_d2(_mask(wh, name))
+    return _D2_TWO_PASS[(wh, name)]
+
+
+BRUTE_MAX_WH = 257
+LARGE_BATCHES = (('rand04',), ('full',), ('empty',), ('rand001', 'empty', 'corner_br'))
+
+
+def distance_field_batches(wh):
+    """-> list of (names, uint8 [B,wh,wh], int32 [B,wh,wh] reference) for the GPU test.  Up to BRUTE_MAX_WH: all of mask_batches against brute
+    force.  Above: LARGE_BATCHES (dense, full, empty, and an empty frame between two others) against the two-pass."""
+    if wh <= BRUTE_MAX_WH:
+        return [(names, masks, np.stack([reference_d2(wh, n) for n in names])) for names, masks in mask_batches(wh)]
+    mc = mask_cases(wh)
+    return [(names, np.stack([mc[n] for n in names]), np.stack([reference_d2_two_pass(wh, n) for n in names])) for names in LARGE_BATCHES]
 
 
 # ------------------------------------------------------------------ the two energies
@@ -292,9 +344,30 @@ def conditions_hold(cond):
     return cond['cell'] > 1e-3 and cond['tau'] > 1e-3 and cond['gap'] > 1e-4
 
 
+# the constants of csrc/silfit.hip that decide which path a case takes
+LANES = 256                # BLK: lanes of a workgroup = lattice points of a chunk = vertices of a partial sum
+VERTEX_TILE = 6912         # VTILE: projected vertices one LDS tile of the search holds
+GATHER_TILE = 2048         # PTILE: entries of the nearest list one LDS tile of the gather holds
+MAX_WORKGROUPS = 32        # MAX_NBP: workgroups per body of the search
+
+
+def path_facts(spec):
+    """(nverts, wh, lattice, ...) -> the paths of csrc/silfit.hip the case takes: 'vertex_tiles' (LDS tiles of the search; above one, the
+    barriers and reloads sit inside the chunk loop), 'gather_tiles', 'chunks' of 256 lattice points, 'trips' = (fewest, most) chunks walked by a
+    workgroup of the search, 'finish_trips' of sil_finish_kernel's strided sum over the per-256-vertex partials, 'wh'"""
+    nverts, wh, lattice = spec[:3]
+    up = lambda a, b: -(-a // b)
+    nl = up(wh, min(lattice, wh))
+    chunks = up(nl * nl, LANES)
+    groups = min(chunks, MAX_WORKGROUPS)
+    return {'vertex_tiles': up(nverts, VERTEX_TILE), 'gather_tiles': up(nl * nl, GATHER_TILE), 'chunks': chunks, 'trips': (chunks // groups, up(chunks, groups)),
+            'finish_trips': up(up(nverts, LANES), LANES), 'wh': wh}
+
+
 # (nverts, wh, lattice, tau, B, first seed, keyword arguments): every value the GPU test is asked to cover appears at least once, with the sizes at
-# which the kernels change path: more vertices than one LDS tile of the search holds (6912), more lattice points than one LDS tile of the gather
-# holds (2048), more chunks of 256 lattice points than workgroups per body (32)
+# which the kernels change path; tests/test_silfit_cases_cpu.py (test_energy_cases_reach_every_path) asserts, from path_facts, which paths these
+# cases reach -- a path named there cannot lose its last case unnoticed.  The first seeds of the cases above 8192 lattice points or 65 536
+# vertices are those at which get_energy_case qualifies at once (a try at wh = 1024 costs a 1024 x 1024 transform).
 ENERGY_SPECS = {
     'v1_wh2': (1, 2, 1, 0.0, 1, 6100, {}),
     'v63_wh16_l3': (63, 16, 3, 1.5, 3, 6200, {'empty_body': 1}),
@@ -304,6 +377,11 @@ ENERGY_SPECS = {
     'v257_wh256_l3': (257, 256, 3, 0.0, 1, 6600, {}),
     'v7000_wh16_l1': (7000, 16, 1, 1.5, 1, 6700, {}),
     'v6890_wh256_l4': (6890, 256, 4, 1.5, 3, 6835, {'empty_body': 1, 'tie': True}),
+    'v257_wh96_l1': (257, 96, 1, 1.5, 1, 8100, {}),                             # 36 chunks on 32 workgroups: four of them take two
+    'v7000_wh96_l1': (7000, 96, 1, 0.0, 1, 8207, {}),                           # the same with two vertex tiles
+    'v65_wh320_l3': (65, 320, 3, 1.5, 3, 8307, {'empty_body': 1}),              # 45 chunks, wh above 256
+    'v65537_wh16_l2': (65537, 16, 2, 0.0, 1, 8400, {}),                         # ten vertex tiles, 257 partial sums
+    'v65_wh1024_l8': (65, 1024, 8, 1.5, 1, 8535, {}),                           # 64 chunks: two whole trips in every workgroup, the largest wh
 }
 _CASES = {}
 

@@ -1,17 +1,22 @@
 """GPU: straps_silhouette_energy (csrc/silfit.hip) against the float64 restatement of tests/silfit_cases.py: energy2, dverts, dcam, nearest.
 
 Every output and the workspace sit behind redzone guards, every input ends against a NaN margin; the distance field handed to the kernel is the
-CPU's (two_pass_d2), so that this file tests the energy alone.  The cases (silfit_cases.ENERGY_SPECS) cover nverts 1, 63, 64, 65, 257, 6890
-and 7000 (more than the 6912 vertices one LDS tile of the search holds), wh 2, 16, 33, 256, lattice 1, 3, 4 and wh + 1 (a single point), tau 0
-and 1.5, batches of 1 and 3, vertices beyond every side and corner, an empty mask inside a batch, foreground without a valid lattice point, and
-two vertices at one position.  tests/test_silfit_cases_cpu.py asserts the input conditions that keep fp32 and float64 on the same branch.
+CPU's (two_pass_d2), so that this file tests the energy alone.  The cases (silfit_cases.ENERGY_SPECS) cover nverts 1, 63, 64, 65, 257, 6890,
+7000 (more than the 6912 vertices one LDS tile of the search holds) and 65537 (ten tiles, and 257 partial sums for the finish to add in two
+strided trips), wh 2, 16, 33, 96, 256, 320 and 1024 (the limit), lattice 1, 2, 3, 4, 8 and wh + 1 (a single point), tau 0 and 1.5, batches of 1
+and 3, vertices beyond every side and corner, an empty mask inside a batch, foreground without a valid lattice point, and two vertices at one
+position.  Three cases have more chunks of 256 lattice points than the 32 workgroups the search gives a body -- 36 (workgroups 0..3 walk two
+chunks, the others one; once with one vertex tile and once with two, so that the barriers and tile reloads run inside the chunk loop), 45 and 64
+(two whole trips each).  tests/test_silfit_cases_cpu.py asserts the input conditions that keep fp32 and float64 on the same branch, and
+(test_energy_cases_reach_every_path) that the cases reach each of these paths.
 
 `nearest`: for EVERY valid lattice point the reported vertex's float64 distance must be within 1e-5 relative of the true minimum; the float64
 energies and gradients are then evaluated with the reported vertices.
 Bounds: energies 1e-5 relative, gradients 1e-4 of the largest magnitude in the tensor (the keypoint fit's bars; an fp32 mean of n terms is
 off by at most n * 2^-23 relative in the worst case, 8e-4 at 6890 vertices).
-Measured on MI355X, worst over all cases: nearest excess 0 (the float64 vertex everywhere), energy 8.1e-7, dverts 6.2e-6, dcam 8.6e-7 -- all
-below a third of their bounds (DESIGN.md has the same figures)."""
+Measured on MI355X, worst over all cases: nearest excess 0 (the float64 vertex everywhere), energy 1.6e-6 (the mean over 65537 vertices, whose
+worst case by that model is 7.8e-3; 8.1e-7 over the other cases), dverts 6.2e-6, dcam 8.6e-7 -- all below a third of their bounds.  The cases
+beyond 8192 lattice points, 256 pixels or 65536 vertices alone: energy 1.6e-6, dverts 5.0e-6, dcam 3.9e-7 (DESIGN.md has the same figures)."""
 import numpy as np
 import pytest
 import torch
@@ -119,7 +124,7 @@ def test_energy_and_gradients_vs_float64(dev, name):
     assert same(got, run(dev, case)) and same(got, run(dev, case, ld_cam=157))
 
 
-@pytest.mark.parametrize('name', ['v63_wh16_l3', 'v65_wh33_l4', 'v6890_wh256_l4'])
+@pytest.mark.parametrize('name', ['v63_wh16_l3', 'v65_wh33_l4', 'v6890_wh256_l4', 'v65_wh320_l3'])
 def test_a_body_alone_equals_the_body_in_its_batch(dev, name):
     case = SC.get_energy_case(name)
     whole = run(dev, case)
@@ -128,7 +133,7 @@ def test_a_body_alone_equals_the_body_in_its_batch(dev, name):
         assert same(alone, {k: v[b:b + 1] for k, v in whole.items()}), (name, b)
 
 
-@pytest.mark.parametrize('name', ['v65_wh33_l4', 'v7000_wh16_l1'])
+@pytest.mark.parametrize('name', ['v65_wh33_l4', 'v7000_wh16_l1', 'v7000_wh96_l1'])
 def test_each_output_alone(dev, name):
     case = SC.get_energy_case(name)
     whole = run(dev, case)

@@ -1,6 +1,8 @@
 """CPU: the float64 reference of the silhouette fit (tests/silfit_cases.py) is itself checked -- the brute-force distance transform against
-a two-pass restatement, the autograd gradient against central differences, the input conditions of every energy case, and the float64
-composed fit of the standard trajectory case, whose outcome is the condition of the GPU test's bound."""
+a row-blocked two-pass restatement (all masks up to 257 pixels; sparse masks at 1000 and 1024, which licenses the two-pass as the GPU tests'
+reference above 257), the autograd gradient against central differences, the input conditions of every energy case, the paths of
+csrc/silfit.hip that the energy cases reach, and the float64 composed fit of the standard trajectory case, whose outcome is the condition of
+the GPU test's bound."""
 import numpy as np
 import pytest
 import torch
@@ -14,16 +16,45 @@ def _threads():
     torch.set_num_threads(cpu_threads())
 
 
-@pytest.mark.parametrize('wh', [1, 2, 3, 16, 17, 64, 65, 256])
+def _check_transform(wh, name, m, got):
+    want = SC.reference_d2(wh, name)
+    assert want.dtype == np.int32 and got.dtype == np.int32 and np.array_equal(want, got), (wh, name)
+    assert (want[m != 0] == 0).all()
+    if not m.any():
+        assert (want == 2 * wh * wh).all()
+    else:
+        assert want.max() <= 2 * (wh - 1) ** 2 < 2 * wh * wh
+
+
+@pytest.mark.parametrize('wh', [1, 2, 3, 16, 17, 64, 65, 256, 257])
 def test_brute_force_transform_equals_two_pass(wh):
+    assert wh <= SC.BRUTE_MAX_WH
     for name, m in SC.mask_cases(wh).items():
-        want = SC.reference_d2(wh, name)
-        assert want.dtype == np.int32 and np.array_equal(want, SC.two_pass_d2(m)), (wh, name)
-        assert (want[m != 0] == 0).all()
-        if not m.any():
-            assert (want == 2 * wh * wh).all()
-        else:
-            assert want.max() <= 2 * (wh - 1) ** 2 < 2 * wh * wh
+        _check_transform(wh, name, m, SC.two_pass_d2(m))
+
+
+@pytest.mark.parametrize('wh', [1000, 1024])
+def test_brute_force_transform_equals_two_pass_on_sparse_masks_at_the_largest_sizes(wh):
+    """what licenses the row-blocked two-pass as the GPU tests' reference above 257 pixels: on masks sparse enough for brute force (about 1e8
+    integer operations each) the two agree exactly, at a size that is no multiple of 64 and at the limit"""
+    cases = SC.sparse_mask_cases(wh)
+    assert tuple(cases) == SC.SPARSE and 50 <= int((cases['rand1e4'] != 0).sum()) <= 200
+    for name, m in cases.items():
+        _check_transform(wh, name, m, SC.reference_d2_two_pass(wh, name))
+
+
+def test_row_blocking_changes_nothing():
+    """the blocked row pass against all rows at once, and against a block size that does not divide wh"""
+    m = SC.mask_cases(65)
+    whole = {k: SC.two_pass_d2(v) for k, v in m.items()}
+    keep = SC.ROW_BLOCK
+    try:
+        for block in (1, 7, 65, 1000):
+            SC.ROW_BLOCK = block
+            for k, v in m.items():
+                assert np.array_equal(SC.two_pass_d2(v), whole[k]), (block, k)
+    finally:
+        SC.ROW_BLOCK = keep
 
 
 def test_autograd_gradient_matches_central_differences():
@@ -81,6 +112,40 @@ def test_energy_cases_meet_the_input_conditions(name):
         g = SC.grid_coords(case['verts'].double(), case['cam'].double(), wh)[:, :8]
         out = ((g < 0) | (g > wh - 1)).sum(dim=2)
         assert bool((out[:, :4] == 1).all()) and bool((out[:, 4:] == 2).all())
+
+
+PATHS = {
+    'one vertex tile': lambda f: f['vertex_tiles'] == 1,
+    'more than one vertex tile': lambda f: f['vertex_tiles'] > 1,
+    'one gather tile': lambda f: f['gather_tiles'] == 1,
+    'more than one gather tile': lambda f: f['gather_tiles'] > 1,
+    'no more chunks than workgroups': lambda f: f['chunks'] <= SC.MAX_WORKGROUPS,
+    'more chunks than workgroups, ragged trips': lambda f: f['chunks'] > SC.MAX_WORKGROUPS and f['trips'][0] < f['trips'][1],
+    'more chunks than workgroups, equal trips': lambda f: f['chunks'] > SC.MAX_WORKGROUPS and f['trips'][0] == f['trips'][1],
+    'more chunks than workgroups with more than one vertex tile': lambda f: f['chunks'] > SC.MAX_WORKGROUPS and f['vertex_tiles'] > 1,
+    'more than 256 partial sums in the finish': lambda f: f['finish_trips'] > 1,
+    'wh above 256': lambda f: f['wh'] > 256,
+    'wh = 1024': lambda f: f['wh'] == 1024,
+}
+
+
+def test_path_facts():
+    assert (SC.LANES, SC.VERTEX_TILE, SC.GATHER_TILE, SC.MAX_WORKGROUPS) == (256, 6912, 2048, 32)
+    f = SC.path_facts((6912, 256, 2))                   # 16384 points: 64 chunks, two whole trips
+    assert f == {'vertex_tiles': 1, 'gather_tiles': 8, 'chunks': 64, 'trips': (2, 2), 'finish_trips': 1, 'wh': 256}
+    f = SC.path_facts((6913, 91, 1))                    # 8281 points: 33 chunks, workgroup 0 takes two
+    assert f == {'vertex_tiles': 2, 'gather_tiles': 5, 'chunks': 33, 'trips': (1, 2), 'finish_trips': 1, 'wh': 91}
+    f = SC.path_facts((65537, 16, 17))                  # a lattice above wh - 1: the single point
+    assert f == {'vertex_tiles': 10, 'gather_tiles': 1, 'chunks': 1, 'trips': (1, 1), 'finish_trips': 2, 'wh': 16}
+    assert SC.path_facts((65536, 16, 4))['finish_trips'] == 1
+
+
+@pytest.mark.parametrize('path', sorted(PATHS))
+def test_energy_cases_reach_every_path(path):
+    """every path of csrc/silfit.hip's energy kernels that depends on the sizes is taken by at least one case of ENERGY_SPECS"""
+    reached = [name for name, spec in SC.ENERGY_SPECS.items() if PATHS[path](SC.path_facts(spec))]
+    print(path, '<-', reached)
+    assert reached, 'no case of ENERGY_SPECS reaches: ' + path
 
 
 def test_float64_fit_of_the_standard_trajectory_case_reaches_a_quarter():
