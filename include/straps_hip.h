@@ -1146,6 +1146,42 @@ int straps_fit_adam(const straps_fit_opts_t* opts, float* est /*[B][157] in/out*
         float* exp_avg, float* exp_avg_sq, float* energy, long long ld_energy, long long col, float* grad,
         float* best_est, float* best_energy, int step, int first, int update, long long batch, void* stream);
 
+/* ---- the 3-D scan term of test-time fitting (csrc/scanfit.hip; added without a version change) ------------------------------------
+ * The two-sided nearest-point distance between a body and a cloud of 3-D points (a depth camera's or a scanner's): every point pulls
+ * its nearest vertex towards it, every vertex is pulled towards its nearest point.  Point to point; no normals, no landmarks, no grid.
+ *
+ * straps_scan_energy, per body, fp32:
+ *   inputs        verts [B][nverts][3]; trans: the body's translation t in the first three floats of a row of stride ld_trans >= 3 (a
+ *                 row of est in the scan fit, where t takes the place of the camera); points [B][npoints][3], a point is VALID iff its
+ *                 three coordinates are finite -- NaN padding is how a ragged batch is passed.
+ *   definitions   X_v = verts_v + t, one rounding per component;  d2(i, v) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) with d = X_v - p_i;
+ *                 rho(r2) = sigma^2 r2 / (sigma^2 + r2) for sigma > 0, else r2 (the robust kernel of straps_fit_keypoints; sigma in
+ *                 metres).  Coordinates are taken to be small enough for every d2 between valid partners to be finite: a partner at an
+ *                 infinite d2 does not count as one.
+ *   scan to mesh  for every valid point, n_i = the lowest v among the minima of d2(i, .);  E_s2m = (1 / max(1, n_valid)) sum_i
+ *                 rho(d2(i, n_i)), whose gradient goes to X_{n_i} alone.
+ *   mesh to scan  for every vertex, m_v = the lowest valid i among the minima of d2(., v);  E_m2s = (1 / nverts) sum_v rho(d2(m_v, v)).
+ *   partial scans w_m2s == 0 skips the mesh-to-scan search: E_m2s is reported as 0 and nearest_point as -1 (half the time); likewise
+ *                 w_s2m == 0 (E_s2m 0, nearest_vertex -1).
+ *   empty scan    a body without a valid point gets both energies 0, all gradients 0 and both index lists -1.
+ *   outputs (each may be NULL, at least one must be given): energy2 [B][2] = { E_s2m, E_m2s } unweighted; dverts [B][nverts][3] = the
+ *   gradient of w_s2m E_s2m + w_m2s E_m2s; dtrans [B][3] = the sum of the dverts rows in a fixed order; nearest_vertex [B][npoints]
+ *   int32 = n_i, -1 at invalid points; nearest_point [B][nverts] int32 = m_v.
+ *   workspace (16-byte aligned): straps_scan_energy_workspace_bytes = batch * (24 * nverts + 28 * npoints + 16 * ceil(nverts / 256)
+ *   + 4 * ceil(npoints / 256) + 16) bytes, 0 for an invalid request.  1 <= nverts <= 2^20, 1 <= npoints <= 2^20, 1 <= batch < 2^19,
+ *   sigma >= 0 and both weights >= 0, all three finite.
+ *
+ * Arguments are checked before any HIP call.  It launches on `stream`, allocates nothing, never synchronises and is capturable; it uses
+ * no float atomics (the minima over the tiles of the distance matrix are merged with integer minimum atomics, which no order changes)
+ * and is bit-reproducible; a body's result depends on nothing but that body's inputs.                                               */
+typedef struct {
+    float sigma, w_s2m, w_m2s;  /* sigma in metres */
+} straps_scan_opts_t;
+size_t straps_scan_energy_workspace_bytes(long long batch, int nverts, int npoints);
+int straps_scan_energy(const float* verts, const float* trans, int ld_trans, const float* points, const straps_scan_opts_t* opts,
+        float* energy2, float* dverts, float* dtrans, int32_t* nearest_vertex, int32_t* nearest_point,
+        void* workspace, long long batch, int nverts, int npoints, void* stream);
+
 /* ---- one body shape per subject across frames (csrc/fit_subjects.hip; added without a version change) ----------------------------
  * straps_fit_adam_subjects: straps_fit_adam with the ten shape coefficients tied across the frames of a subject -- the update step of
  * a fit loop in which several frames show one person.  The arguments it shares with straps_fit_adam mean what they mean there.

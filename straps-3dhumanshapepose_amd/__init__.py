@@ -18,7 +18,7 @@ from .multi_task_loss import HomoscedasticUncertaintyWeightedMultiTaskLoss  # no
 from .nmr_renderer import NMRRenderer, WeakPerspectiveSilhouetteRenderer, WeakPerspectiveMeshRenderer, vertex_face_table  # noqa: F401
 from .metrics import EvalMetricsTracker  # noqa: F401
 from .predict import Predictor, create_proxy_representation_batch, heatmap_patch  # noqa: F401
-from .fit import KeypointFitter, SilhouetteFitter, SubjectFitter, MeasurementFitter, distance_field, pack_fit_model  # noqa: F401
+from .fit import KeypointFitter, SilhouetteFitter, SubjectFitter, ScanFitter, MeasurementFitter, distance_field, pack_fit_model  # noqa: F401
 from .measure import BodyMeasurer, default_measurements, tape_measurements, posed_measurements  # noqa: F401
 from .validation import ValStep, EpochHistory  # noqa: F401
 from . import cam_utils, label_conversions, augmentation, metrics, checkpoint_utils, image_utils, device_rng, measure, validation  # noqa: F401

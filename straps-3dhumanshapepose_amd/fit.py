@@ -17,6 +17,11 @@ tau 1.5 px) are those of a float64 prototype on the synthetic model as well: unt
 
 `SubjectFitter` is that loop for several frames of one person: cam and pose per frame, ONE shape per subject (straps_fit_adam_subjects and
 straps_subject_mean_rows, csrc/fit_subjects.hip, in the place of straps_fit_adam).
+
+`ScanFitter` takes a 3-D scan of the person as its target instead of images: the same loop with straps_scan_energy (csrc/scanfit.hip), the
+two-sided nearest-point distance between the posed vertices and the scan's points, in the place of the silhouette term, and a translation
+in metres in the place of the camera.  Its defaults (weights 100 and 100, sigma 0, lr 0.01) are a float64 prototype's on the synthetic
+model as well: untuned on real scans.
 """
 import ctypes as C
 
@@ -346,6 +351,160 @@ class SilhouetteFitter(KeypointFitter):
                'best': {'cam_wp': best[:, :3], 'pose': best[:, 3:147], 'shape': best[:, 147:], 'energy': best_e},
                'energy_terms': torch.cat([buf['e_kp'], buf['energy2']], dim=1),
                'joints2D': cam_utils.undo_keypoint_normalisation(buf['kp2d'], self.img_wh),
+               'state': {'exp_avg': m, 'exp_avg_sq': v, 'step': step0 + self.iters}}
+        if trace:
+            out['trace'] = energy
+        return out
+
+
+def scan_energy_raw(verts, trans, ld_trans, points, opts, energy2, dverts, dtrans, nearest_vertex, nearest_point, workspace):
+    """one straps_scan_energy call on contiguous GPU tensors (None -> NULL); trans: a tensor or a raw device address"""
+    tp = C.c_void_p(trans) if isinstance(trans, int) else hipabi.ptr(trans)
+    hipabi.check(hipabi.lib().straps_scan_energy(hipabi.ptr(verts), tp, ld_trans, hipabi.ptr(points), C.byref(opts), hipabi.ptr(energy2), hipabi.ptr(dverts),
+                                                 hipabi.ptr(dtrans), hipabi.ptr(nearest_vertex), hipabi.ptr(nearest_point), hipabi.ptr(workspace), verts.shape[0],
+                                                 verts.shape[1], points.shape[1], hipabi.stream_ptr()), 'straps_scan_energy')
+
+
+class ScanFitter(KeypointFitter):
+    """`ScanFitter(smpl)(transl, pose6d, shape, points)`: registers the body to a 3-D scan.  Minimises w_s2m E_s2m + w_m2s E_m2s of
+    straps_scan_energy (include/straps_hip.h: every point pulls its nearest vertex, every vertex is pulled to its nearest point) plus
+    KeypointFitter's pose and shape priors, by the same Adam.  In this mode the first three columns of a body's row hold the translation t
+    in metres, where the image fitters keep (s, tx, ty); lr[0] is its learning rate.  points [B,P,3]: a point with a NaN or an infinite
+    coordinate does not count, which is how scans of different sizes share a batch.  w_m2s = 0 is the mode for partial scans (vertices the
+    scan does not cover are pulled nowhere) and costs half the time.  sigma > 0 (metres) bounds the pull of far partners.
+    The defaults (weights 100 and 100, sigma 0, lr 0.01, lambda 1e-3) are a float64 prototype's on the synthetic model of this package:
+    untuned on real scans, and no real SMPL model was available when they were chosen."""
+
+    def __init__(self, smpl, iters=100, lr=0.01, sigma=0.0, w_s2m=100., w_m2s=100., lambda_pose=1e-3, lambda_shape=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 keypoints=None):
+        KeypointFitter.__init__(self, smpl, keypoints, iters, lr, 0.0, lambda_pose, lambda_shape, config.REGRESSOR_IMG_WH, betas, eps)
+        self.smpl = smpl
+        ok = lambda x: np.isfinite(x) and x >= 0
+        if not (ok(float(sigma)) and ok(float(w_s2m)) and ok(float(w_m2s))):
+            raise ValueError('ScanFitter: sigma, w_s2m and w_m2s must be finite and not negative')
+        self.sigma, self.w_s2m, self.w_m2s = float(sigma), float(w_s2m), float(w_m2s)
+
+    def scan_opts(self):
+        return hipabi.ScanOptsStruct(self.sigma, self.w_s2m, self.w_m2s)
+
+    def _start_translation(self, pose6d, shape, pts):
+        """the centroid of the valid points minus the centroid of the start mesh (plain torch; once per call)"""
+        B = pose6d.shape[0]
+        R = rot6d_to_rotmat(pose6d.detach().contiguous()).view(B, 24, 3, 3).contiguous()
+        verts = self.smpl.forward_arrays(shape.detach().contiguous(), R, want_joints=False)
+        verts = verts[0] if isinstance(verts, (tuple, list)) else verts
+        valid = torch.isfinite(pts).all(dim=2, keepdim=True)
+        n = valid.sum(dim=1).clamp(min=1).to(torch.float32)
+        centroid = torch.where(valid, pts, torch.zeros_like(pts)).sum(dim=1) / n
+        return (centroid - verts.mean(dim=1)) * (valid.any(dim=1)).to(torch.float32)
+
+    def _scan_inputs(self, transl, pose6d, shape, points, prior):
+        hipabi.require_gpu_tensor(pose6d, 'pose6d', torch.float32)
+        B = pose6d.shape[0]
+        hipabi.require_gpu_tensor(points, 'points', torch.float32)
+        if points.dim() != 3 or points.shape[0] != B or points.shape[2] != 3 or not 1 <= points.shape[1] <= (1 << 20):
+            raise RuntimeError('ScanFitter: points must be [%d,P,3] with 1 <= P <= 2^20, got %s' % (B, tuple(points.shape)))
+        pts = points.detach().contiguous()
+        hipabi.require_gpu_tensor(shape, 'shape', torch.float32)
+        if tuple(pose6d.shape) != (B, 144) or tuple(shape.shape) != (B, 10):
+            raise RuntimeError('ScanFitter: pose6d must be [B,144] and shape [B,10], got %s and %s' % (tuple(pose6d.shape), tuple(shape.shape)))
+        if transl is None:
+            transl = self._start_translation(pose6d, shape, pts)
+        hipabi.require_gpu_tensor(transl, 'transl', torch.float32)
+        if tuple(transl.shape) != (B, 3):
+            raise RuntimeError('ScanFitter: transl must be [%d,3], got %s' % (B, tuple(transl.shape)))
+        est = torch.cat([transl.detach(), pose6d.detach(), shape.detach()], dim=1)
+        if prior is None:
+            est0 = est.clone()      # (the start: est itself moves)
+        else:
+            for p in (prior if isinstance(prior, (tuple, list)) else (prior,)):
+                hipabi.require_gpu_tensor(p, 'prior', torch.float32)
+            est0 = (torch.cat([p.detach() for p in prior], dim=1) if isinstance(prior, (tuple, list)) else prior.detach()).contiguous()
+            if tuple(est0.shape) != (B, NE):
+                raise RuntimeError('ScanFitter: prior must be [B,157] or a (transl, pose6d, shape) triple, got %s' % (tuple(est0.shape),))
+        return est, est0, pts
+
+    def _scan_buffers(self, B, dev, P):
+        L = hipabi.lib()
+        V = self.smpl.v_template.shape[0]
+        f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
+        unit = torch.zeros(B, 3, device=dev, dtype=torch.float32)
+        unit[:, 0] = 1.0
+        return {'R': f(B, 24, 3, 3), 'betas': f(B, 10), 'verts': f(B, V, 3), 'dverts': f(B, V, 3), 'dtrans': f(B, 3), 'energy2': f(B, 2), 'drot': f(B, 24, 3, 3),
+                'dbetas': f(B, 10), 'dx6': f(B, 144), 'e_kp': f(B, 1), 'g_kp': f(B, NE), 'est_kp': f(B, NE), 'cam_unit': unit,
+                'targets': torch.zeros(B, self.n_kp, 2, device=dev, dtype=torch.float32), 'conf': torch.zeros(B, self.n_kp, device=dev, dtype=torch.float32),
+                'nearest_vertex': torch.empty(B, P, device=dev, dtype=torch.int32), 'nearest_point': torch.empty(B, V, device=dev, dtype=torch.int32),
+                'ws': torch.empty(L.straps_scan_energy_workspace_bytes(B, V, P) // 16 + 1, 2, device=dev, dtype=torch.float64),
+                'ws_bwd': f(L.straps_smpl_bwd_workspace_bytes(B, 0) // 4)}
+
+    def _scan_terms(self, est, est0, pts, buf):
+        """the six evaluating entry points of one iteration at `est` (steps 1 to 6 of the loop); the results are left in `buf`"""
+        L, st, B = hipabi.lib(), hipabi.stream_ptr(), est.shape[0]
+        x6 = C.c_void_p(est.data_ptr() + 12)
+        hipabi.check(L.straps_rot6d_fwd(x6, NE, 24, hipabi.ptr(buf['R']), B, st), 'straps_rot6d_fwd')
+        buf['betas'].copy_(est[:, 147:])
+        self.smpl.forward_arrays(buf['betas'], buf['R'], want_joints=False, out_verts=buf['verts'])
+        scan_energy_raw(buf['verts'], est, NE, pts, self.scan_opts(), buf['energy2'], buf['dverts'], buf['dtrans'], buf['nearest_vertex'], buf['nearest_point'],
+                        buf['ws'])
+        hipabi.check(L.straps_smpl_bwd(C.byref(self.smpl._model_struct()), hipabi.ptr(buf['betas']), hipabi.ptr(buf['R']), hipabi.ptr(buf['dverts']), None,
+                                       hipabi.ptr(buf['dbetas']), hipabi.ptr(buf['drot']), hipabi.ptr(buf['ws_bwd']), B, 0, st), 'straps_smpl_bwd')
+        hipabi.check(L.straps_rot6d_bwd(x6, NE, 24, hipabi.ptr(buf['drot']), hipabi.ptr(buf['dx6']), 144, B, st), 'straps_rot6d_bwd')
+        # the priors: all confidences zero, and a camera of (1, 0, 0) in the translation's place, so that nothing rests on how an unevaluated
+        # residual treats the camera
+        buf['est_kp'].copy_(est)
+        buf['est_kp'][:, :3].copy_(buf['cam_unit'])
+        fit_keypoints_raw(self._struct, self.opts(0), buf['est_kp'], est0, buf['targets'], buf['conf'], None, None, buf['e_kp'], buf['g_kp'], None, None, None)
+
+    @hipabi.on_tensor_device
+    def evaluate(self, transl, pose6d, shape, points, prior=None):
+        """-> (energy [B], grad [B,157], terms [B,3] = (the priors, E_s2m, E_m2s; the scan terms unweighted)) at the given parameters"""
+        est, est0, pts = self._scan_inputs(transl, pose6d, shape, points, prior)
+        B, dev = est.shape[0], est.device
+        buf = self._scan_buffers(B, dev, pts.shape[1])
+        self._scan_terms(est, est0, pts, buf)
+        energy = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        grad = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        fit_adam_raw(self.opts(), est, buf['g_kp'], buf['dtrans'], buf['dx6'], buf['dbetas'], buf['e_kp'], buf['energy2'], self.w_s2m, self.w_m2s, None, None,
+                     energy, 0, grad, None, None, 0, True, False)
+        return energy[:, 0], grad, torch.cat([buf['e_kp'], buf['energy2']], dim=1)
+
+    @hipabi.on_tensor_device
+    def __call__(self, transl, pose6d, shape, points, prior=None, state=None, trace=False):
+        """transl [B,3] (metres; None: the centroid of the valid points minus the centroid of the start mesh), pose6d [B,144], shape [B,10],
+        points [B,P,3], prior: the centre of the pose / shape priors ([B,157] or a (transl, pose6d, shape) triple; None = the start), state:
+        the 'state' of an earlier call.
+        -> {'transl' [B,3], 'pose' [B,144], 'shape' [B,10], 'pose_rotmats' [B,24,3,3], 'verts' [B,V,3] (the final posed vertices, translation
+        added), 'energy0' [B], 'energy' [B] (at the returned parameters), 'energy_terms' [B,3] = (the priors, E_s2m, E_m2s), 'nearest_vertex'
+        [B,P] int32 (-1 at invalid points), 'nearest_point' [B,V] int32, 'best': {'transl', 'pose', 'shape', 'energy'} (the iterate of the
+        smallest energy), 'state', 'trace' [B,iters+1] if asked}.  iters + 1 evaluations, iters updates; every iteration is rot6d forward, SMPL
+        forward, straps_scan_energy, SMPL backward, rot6d backward, straps_fit_keypoints with iters = 0 (the priors), straps_fit_adam, on
+        buffers allocated before the loop.  The inputs are not modified.  Never synchronises; after one warm-up call at the same shapes it can
+        be captured in torch.cuda.graph."""
+        est, est0, pts = self._scan_inputs(transl, pose6d, shape, points, prior)
+        B, dev = est.shape[0], est.device
+        if state is None:
+            m, v, step0 = torch.zeros(B, NE, device=dev), torch.zeros(B, NE, device=dev), 0
+        else:
+            for k in ('exp_avg', 'exp_avg_sq'):
+                hipabi.require_gpu_tensor(state[k], "state['%s']" % k, torch.float32)
+                if tuple(state[k].shape) != (B, NE):
+                    raise RuntimeError("ScanFitter: state['%s'] must be [%d,157], got %s" % (k, B, tuple(state[k].shape)))
+            m, v = (state[k].detach().clone(memory_format=torch.contiguous_format) for k in ('exp_avg', 'exp_avg_sq'))
+            step0 = int(state['step'])
+        buf = self._scan_buffers(B, dev, pts.shape[1])
+        energy = torch.empty(B, self.iters + 1, device=dev, dtype=torch.float32)
+        best = torch.empty(B, NE, device=dev, dtype=torch.float32)
+        best_e = torch.empty(B, device=dev, dtype=torch.float32)
+        opts = self.opts()
+        for i in range(self.iters + 1):
+            self._scan_terms(est, est0, pts, buf)
+            fit_adam_raw(opts, est, buf['g_kp'], buf['dtrans'], buf['dx6'], buf['dbetas'], buf['e_kp'], buf['energy2'], self.w_s2m, self.w_m2s, m, v,
+                         energy, i, None, best, best_e, step0 + i, i == 0, i < self.iters)
+        out = {'transl': est[:, :3], 'pose': est[:, 3:147], 'shape': est[:, 147:], 'pose_rotmats': buf['R'], 'verts': buf['verts'] + est[:, None, :3],
+               'energy0': energy[:, 0], 'energy': energy[:, self.iters],
+               'best': {'transl': best[:, :3], 'pose': best[:, 3:147], 'shape': best[:, 147:], 'energy': best_e},
+               'energy_terms': torch.cat([buf['e_kp'], buf['energy2']], dim=1),
+               'nearest_vertex': buf['nearest_vertex'], 'nearest_point': buf['nearest_point'],
                'state': {'exp_avg': m, 'exp_avg_sq': v, 'step': step0 + self.iters}}
         if trace:
             out['trace'] = energy

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, 'libstraps_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'straps_hip.h')
 SOURCES = ['abi.hip', 'augment.hip', 'pose.hip', 'ief.hip', 'elementwise.hip', 'conv.hip', 'conv_x3.hip', 'conv_x3_lean.hip', 'conv_bf16.hip', 'conv_x3f.hip', 'conv_wgrad_x3f.hip', 'stem.hip', 'stem_dgrad.hip', 'smpl.hip',
            'smpl_bwd.hip', 'backward.hip', 'conv_wgrad.hip', 'train.hip', 'metrics.hip', 'image.hip', 'raster.hip', 'exchange.hip',
-           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'fit_subjects.hip', 'render.hip', 'measure.hip', 'val.hip', 'measure_tape.hip', 'measure_bwd.hip', 'measure_tape_bwd.hip']
+           'regressor.hip', 'regressor_train.hip', 'predict.hip', 'eval.hip', 'fit.hip', 'silfit.hip', 'scanfit.hip', 'fit_subjects.hip', 'render.hip', 'measure.hip', 'val.hip', 'measure_tape.hip', 'measure_bwd.hip', 'measure_tape_bwd.hip']
 
 _lib = None
 LINK_LIBS = ['-ldl']
@@ -181,6 +181,11 @@ class FitOptsStruct(C.Structure):
 class SilFitOptsStruct(C.Structure):
     """mirror of straps_silfit_opts_t"""
     _fields_ = [('wh', C.c_int32), ('lattice', C.c_int32), ('tau', C.c_float), ('w_in', C.c_float), ('w_out', C.c_float)]
+
+
+class ScanOptsStruct(C.Structure):
+    """mirror of straps_scan_opts_t"""
+    _fields_ = [('sigma', C.c_float), ('w_s2m', C.c_float), ('w_m2s', C.c_float)]
 
 
 class RenderOptsStruct(C.Structure):
@@ -354,6 +359,9 @@ SIGNATURES = {
     'straps_silhouette_energy_workspace_bytes': (_Z, [_L, _I, _I, _I]),
     'straps_silhouette_energy': (_I, [_P, _P, _I, _P, _P, C.POINTER(SilFitOptsStruct)] + [_P] * 5 + [_L, _I, _P]),
     'straps_fit_adam': (_I, [C.POINTER(FitOptsStruct)] + [_P] * 7 + [_F, _F] + [_P] * 3 + [_L, _L] + [_P] * 3 + [_I, _I, _I, _L, _P]),
+    # the 3-D scan term of test-time fitting (csrc/scanfit.hip; added without a version change)
+    'straps_scan_energy_workspace_bytes': (_Z, [_L, _I, _I]),
+    'straps_scan_energy': (_I, [_P, _P, _I, _P, C.POINTER(ScanOptsStruct)] + [_P] * 6 + [_L, _I, _I, _P]),
     # one body shape per subject across frames: the grouped update step and the subjects' mean rows (csrc/fit_subjects.hip; added without a version change)
     'straps_fit_adam_subjects': (_I, [C.POINTER(FitOptsStruct)] + [_P] * 9 + [_F, _F] + [_P] * 5 + [_L, _L, _P, _L] + [_P] * 3 + [_I, _I, _I, _L, _L, _P]),
     'straps_subject_mean_rows': (_I, [_P, _L, _I, _P, _P, _P, _L, _L, _P]),
